@@ -10,7 +10,13 @@ all-reduce per run costs 1.3% vs no RCCL, one per step 2-3%, one per step
 overlapped with the next rollout 5.5% (RCCL's kernel contends for CUs).  value = env-steps (plies summed from the kernel's own
 histogram, passes included) of ALL ranks / max-over-ranks wall time.
 
-Also reported on rank 0 (secondary, same JSON line):
+A plain run does only what that headline needs: set-up, the clock pre-warm, the
+warmup steps, the K timed steps, the output dump if asked for, the JSON line.
+--dump-outputs DIR writes what the last timed step computed (and the histogram
+of the timed steps) as DIR/<name>.npy; the inputs depend on the arguments only,
+so two builds run with the same arguments can be compared array for array.
+
+With --full, also reported on rank 0 (secondary, same JSON line):
   * step_65536 : config 2, one oth_step launch over 65,536 reachable mid-game
     positions (52 algorithmic HBM bytes per step), repeated launches;
   * step_65536_graph: the same 65,536-board launches captured in a HIP graph;
@@ -27,6 +33,7 @@ Also reported on rank 0 (secondary, same JSON line):
     sample of the same workload on the host cores.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload rollout|greedy|step]
+                       [--dump-outputs DIR] [--full]
 Multi-GPU: python bench.py --gpus N ... (starts N rank processes itself), or
            python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 """
@@ -130,7 +137,13 @@ def parse():
     p.add_argument("--workload", choices=["rollout", "greedy", "step"], default="rollout")
     p.add_argument("--games", type=int, default=1 << 20, help="games per GPU per bench step (rollout workloads)")
     p.add_argument("--seed", type=int, default=0x5EED)
-    p.add_argument("--no-secondary", action="store_true", help="skip the secondary step/greedy/cpu measurements")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run the secondary step/greedy/eval/td/book lines and the "
+                        "cpu_baseline (off by default: a plain run times the headline only)")
+    p.add_argument("--no-secondary", action="store_true",
+                   help="with --full: skip the secondary step/greedy/cpu measurements after all")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed step's outputs to DIR/<name>.npy")
     p.add_argument("--cpu-games", type=int, default=250000,
                    help="bounded cpu_baseline sample (games): ~20 s of CPU work on 16 host threads")
     p.add_argument("--allreduce", choices=["async", "sync", "end"], default="end",
@@ -255,14 +268,15 @@ def main():
 
     if args.workload in ("rollout", "greedy"):
         out.update(_bench_rollout(torch, dist, dev, stream, args, policy, world, rank, use_dist, barrier,
-                                  max_over_ranks, args.streams))
+                                  max_over_ranks, args.streams, dump_dir=args.dump_outputs))
     else:
         out.update(_bench_step(ops, torch, dev, stream, args, 65536, world, barrier, max_over_ranks,
-                               index0=rank * 65536))
+                               index0=rank * 65536, dump_dir=args.dump_outputs, rank=rank))
 
-    # secondary + cpu_baseline: rank 0 at N=1 only (BENCH_FORCE_DIST=1 at N=1
-    # takes the N>1 branch below instead, so one GPU exercises it)
-    if world == 1 and not use_dist and not args.no_secondary:
+    # secondary + cpu_baseline, --full only: rank 0 at N=1 only (BENCH_FORCE_DIST=1
+    # at N=1 takes the N>1 branch below instead, so one GPU exercises it)
+    secondary = args.full and not args.no_secondary
+    if world == 1 and not use_dist and secondary:
         sec = {}
 
         def guarded(name, fn):
@@ -315,7 +329,7 @@ def main():
             out["cpu_baseline"] = _cpu_baseline(args, policy if args.workload != "step" else "step")
         except Exception as e:  # noqa: BLE001
             out["cpu_baseline"] = {"error": repr(e)}
-    elif use_dist and not args.no_secondary and args.workload != "step":
+    elif use_dist and secondary and args.workload != "step":
         # N>1: config 2's step over synthetic mid-game positions on every rank
         # (disjoint positions per rank, barrier + max-over-ranks timing), so the
         # step's env-steps/s and HBM roofline are reported at 2/4/8 GPUs too.
@@ -334,8 +348,53 @@ def main():
         dist.destroy_process_group()
 
 
+def _npy_name(name, rank, world):
+    return name + ".npy" if world == 1 else "%s_rank%d.npy" % (name, rank)
+
+
+DUMP_MAX_ROWS = 1 << 20  # rows (games / positions) written per array: 40 B a row at most, under 64 MB in all
+
+
+def _dump_rows(n):
+    """The rows --dump-outputs writes: all n, or a fixed seeded sorted sample of
+    DUMP_MAX_ROWS of them (None = all)."""
+    if n <= DUMP_MAX_ROWS:
+        return None
+    import numpy as np
+
+    return np.sort(np.random.default_rng(0x0D0E).choice(n, DUMP_MAX_ROWS, replace=False))
+
+
+def _u64_halves(t, rows):
+    """An int64 tensor of 64-bit words as float64 [..., 2] = (low, high) 32-bit
+    halves: every bitboard exactly, in a float format."""
+    import numpy as np
+
+    a = t.cpu().numpy().view(np.uint64)
+    if rows is not None:
+        a = a[rows]
+    return np.stack([(a & np.uint64(0xFFFFFFFF)).astype(np.float64), (a >> np.uint64(32)).astype(np.float64)], -1)
+
+
+def _small(t, rows):
+    import numpy as np
+
+    a = t.cpu().numpy()
+    return (a if rows is None else a[rows]).astype(np.float32)
+
+
+def _save(dump_dir, arrays, rows, rank, world):
+    import numpy as np
+
+    os.makedirs(dump_dir, exist_ok=True)
+    if rows is not None:  # the sampled row numbers, beside the arrays they index
+        arrays = dict(arrays, rows=rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(dump_dir, _npy_name(name, rank, world)), a)
+
+
 def _bench_rollout(torch, dist, dev, stream, args, policy, world, rank, use_dist, barrier, max_over_ranks,
-                   nstreams):
+                   nstreams, dump_dir=None):
     """Configs 3/4/5: K bench steps, each one oth_rollout launch over `games`
     fresh games per GPU (+ the histogram all-reduce at N>1).  Steps are issued
     round-robin on `nstreams` HIP streams, each with its own output buffers:
@@ -471,6 +530,18 @@ def _bench_rollout(torch, dist, dev, stream, args, policy, world, rank, use_dist
     median_ms = launch[len(launch) // 2] if len(launch) % 2 else \
         0.5 * (launch[len(launch) // 2 - 1] + launch[len(launch) // 2])
     timed = hists[args.warmup:].sum(0).cpu()  # already global (all-reduced) when distributed
+    if dump_dir:
+        # what a caller of the timed path holds after the last timed step: that
+        # step's output buffers (its stream's set), its own histogram row where
+        # the rows are still per step, and the histogram of all timed steps
+        last = args.warmup + args.steps - 1
+        fb, df, pl = bufs[last % nstreams]
+        rows = _dump_rows(n)
+        arrays = {"final_boards_lo_hi": _u64_halves(fb, rows), "diff": _small(df, rows), "plies": _small(pl, rows),
+                  "hist_timed_steps": timed.numpy().astype("float64")}
+        if not use_dist:
+            arrays["hist_last_step"] = hists[last].cpu().numpy().astype("float64")
+        _save(dump_dir, arrays, rows, rank, world)
     env_steps = int(timed[132])
     games = n * world * args.steps
     # self-check of the sharding: every game of every rank is in the reduced
@@ -528,7 +599,8 @@ def _game_id_ranges(n, world, warmup, steps):
                          for r in range(world)}}
 
 
-def _bench_step(ops, torch, dev, stream, args, n, world, barrier, max_over_ranks, launches=None, index0=0):
+def _bench_step(ops, torch, dev, stream, args, n, world, barrier, max_over_ranks, launches=None, index0=0,
+                dump_dir=None, rank=0):
     """config 2: oth_step over n reachable mid-game positions (inputs resident in
     HBM); at N>1 each rank steps its own positions [index0, index0 + n)."""
     from subproc_amd import _lib
@@ -567,11 +639,17 @@ def _bench_step(ops, torch, dev, stream, args, n, world, barrier, max_over_ranks
     elapsed = max_over_ranks(time.perf_counter() - t0)
     kern_ms = ev0.elapsed_time(ev1) / K
     steps = n * K * world
+    if dump_dir:
+        rows = _dump_rows(n)
+        _save(dump_dir, {"boards_lo_hi": _u64_halves(bo, rows), "turn": _small(to, rows),
+                         "flips_lo_hi": _u64_halves(fl, rows), "legal_next_lo_hi": _u64_halves(ln, rows),
+                         "ret": _small(rt, rows)}, rows, rank, world)
     achieved = n * STEP_BYTES / (kern_ms * 1e-3) / 1e9
     pfile, kernels, stale = load_profile()
     prof = profile_entry(kernels, "step_kernel", n)
     r = {"metric": "env-steps/sec (batched step)", "value": steps / elapsed, "unit": "env-steps/s",
          "n_gpus": world, "batch": n, "launches": K, "us_per_launch": kern_ms * 1e3, "dtype": "u64",
+         "ms_per_step": elapsed / K * 1e3, "higher_is_better": True,
          "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                       "frac": achieved / HBM_PEAK_GBS, "traffic": prof.get("hbm_bytes") if prof else None,
                       "kernel": "step_kernel", "profile": pfile if prof else None, "profile_stale": stale}}

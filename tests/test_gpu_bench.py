@@ -16,7 +16,7 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 def _run(extra, env_extra=None, secondary=False):
     env = dict(os.environ, **(env_extra or {}))
     r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--games", "65536",
-                        "--prewarm-ms", "0"] + ([] if secondary else ["--no-secondary"]) + extra,
+                        "--prewarm-ms", "0"] + (["--full"] if secondary else []) + extra,
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -35,6 +35,37 @@ def test_bench_rollout_line(streams):
     assert 59.5 < out["config"]["env_steps_per_game"] < 61.5
     rf = out["roofline"]
     assert rf["bound"] == "hbm" and 0 < rf["frac"] < 1 and rf["launch_ms"] > 0
+    # a plain run times the headline only: the other lines need --full
+    assert "secondary" not in out and "cpu_baseline" not in out
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed step's arrays (float formats, the
+    bitboards as exact 32-bit halves): they are the games ops.rollout plays
+    over that step's global ids, and the last step's histogram row counts them."""
+    import numpy as np
+    import torch
+
+    from subproc_amd import ops
+    from subproc_amd.dist import bench_game_id0
+
+    steps, warmup, games = 3, 1, 65536
+    out = _run(["--dump-outputs", str(tmp_path / "dump")])
+    got = {f[:-4]: np.load(tmp_path / "dump" / f) for f in os.listdir(tmp_path / "dump")}
+    assert set(got) == {"final_boards_lo_hi", "diff", "plies", "hist_timed_steps", "hist_last_step"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    hist = torch.zeros(133, dtype=torch.int64, device="cuda")
+    r = ops.rollout(games, 0x5EED, bench_game_id0(warmup + steps - 1, 0, 1, games), hist=hist, device="cuda")
+    fb = ops.to_numpy_u64(r.final_boards)
+    halves = got["final_boards_lo_hi"]
+    assert halves.shape == (games, 2, 2)
+    back = halves[..., 0].astype(np.uint64) | (halves[..., 1].astype(np.uint64) << np.uint64(32))
+    assert (back == fb.reshape(games, 2)).all()
+    assert (got["diff"] == r.diff.cpu().numpy()).all() and (got["plies"] == r.plies.cpu().numpy()).all()
+    assert (got["hist_last_step"] == hist.cpu().numpy()).all()
+    assert got["hist_timed_steps"][132] == out["config"]["env_steps"]
 
 
 @pytest.mark.gpu
@@ -81,7 +112,8 @@ def test_bench_two_ranks_line_the_driver_parses():
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
-                        "--steps", str(steps), "--warmup", str(warmup), "--games", str(games), "--prewarm-ms", "0"],
+                        "--steps", str(steps), "--warmup", str(warmup), "--games", str(games), "--prewarm-ms", "0",
+                        "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

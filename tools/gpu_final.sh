@@ -6,7 +6,7 @@
 R=${1:-r04}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 ./tools/gpu_td_check.sh ${R}_td || exit 1
-BENCH_ARGS="--steps 20 --warmup 5" ./tools/gpu_check.sh ${R}_check || exit 1
+BENCH_ARGS="--full --steps 20 --warmup 5" ./tools/gpu_check.sh ${R}_check || exit 1
 ./tools/profile_round.sh $R > /dev/null || exit 1
 cp gpurun_out/prof_$R/summary.json profiles/${R}_profile_summary.json || exit 1
 mkdir -p gpurun_out/${R}_bench2

@@ -9,7 +9,7 @@ mkdir -p $O
 td() { python3 -c "import json,sys; d=[json.loads(l) for l in open(sys.argv[1]) if l.startswith('{')][-1]; t=d['secondary']['td_state_map']; print('%-8s headline %.4e  td %.3f ms (%.3f-%.3f)' % (sys.argv[2], d['value'], t['ms'], t['ms_min'], t['ms_max']))" "$@"; }
 for rep in 1 2; do
   for f in 0 1; do
-    OTH_TD_EMA_FORK=$f timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 > $O/fork${f}_$rep.log 2>&1 || { tail -5 $O/fork${f}_$rep.log; exit 1; }
+    OTH_TD_EMA_FORK=$f timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 > $O/fork${f}_$rep.log 2>&1 || { tail -5 $O/fork${f}_$rep.log; exit 1; }
     td $O/fork${f}_$rep.log fork$f | tee -a $O/fork.txt
   done
 done
