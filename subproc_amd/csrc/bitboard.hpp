@@ -13,9 +13,14 @@
 //     the bit reversal and 32-bit shifts are written in their VOP3 forms;
 //   * Kogge-Stone propagators are computed once per position and shared between
 //     opposite directions (p2R = p2L >> S, p4R = p4L >> 3S);
+//   * the fills G = A | P (runs and the mover's own discs) are read as they
+//     are: no "& O" to get the run sets A.  The reach term of a direction is
+//     sh(G) & ~sh(P), folded into the running OR by one 3-input op with the
+//     first fill step's temporary sh(P) (fill_reach), and the flips take
+//     R & ~A as R & (~G | P) (run_prefix);
 //   * the chosen move's flips come from per-square ray tables in LDS and the
-//     run sets of the analysis (flips_rays), not from more fills; without run
-//     sets (the single step) from one carry along each ray (flips_carry).
+//     fills of the analysis (flips_rays), not from more fills; without an
+//     analysis (the single step) from one carry along each ray (flips_carry).
 //
 // Square sq = x + 8*y (board.py:74-81); rays of board.py:9-17 as shifts:
 //   +1 R (x+1), +8 D (y+1), +9 RD, +7 LD   and their opposites -1 L, -8 U, -9 LU, -7 RU.
@@ -116,14 +121,23 @@ __device__ __forceinline__ u64 ks_step(u64 gen, u64 pro) {
     }
 }
 
-// occluded fill of `gen` along +S (L) or -S through the pair's propagators:
-// covers distances 0..7
+// occluded fill of `src` along +S (L) or -S through the pair's propagators:
+// covers distances 0..7.  The fill G holds the source itself and lies inside
+// src | pro.  PS is the source shifted one step, the temporary of the first
+// Kogge-Stone step (S < 32: a full 64-bit shift); analyse's reach term reads it.
+struct Fill {
+    u64 G, PS;
+};
 template <int S, bool L>
-__device__ __forceinline__ u64 ks(u64 gen, const PairProp& q) {
-    gen = ks_step<S, L>(gen, q.pro);
+__device__ __forceinline__ Fill ks(u64 src, const PairProp& q) {
+    static_assert(S < 32, "the first step's shifted source is a whole 64-bit shift");
+    Fill f;
+    f.PS = sh<S, L>(src);
+    u64 gen = bfi(q.pro, f.PS, src);
     gen = ks_step<2 * S, L>(gen, L ? q.p2L : q.p2R);
     gen = ks_step<4 * S, L>(gen, L ? q.p4L : q.p4R);
-    return gen;
+    f.G = gen;
+    return f;
 }
 
 // 64-bit adds as one v_lshl_add_u64 each (inline asm, for the same reason as
@@ -161,59 +175,89 @@ __device__ __forceinline__ u32 bfrev32(u32 x) {
 }
 __device__ __forceinline__ u64 rev64(u64 x) { return ((u64)bfrev32((u32)x) << 32) | bfrev32((u32)(x >> 32)); }
 
-// All propagators + attached runs of one position (mover P, opponent O).
-// A[i]: opponent discs reachable from a P disc along direction i through
-// opponent discs only (board.py:124-139's "hostile" runs, seen from P).
+// Attached runs and fills of one position (mover P, opponent O).
 // Direction index i: 0:+1 1:-1 2:+8 3:-8 4:+9 5:-9 6:+7 7:-7
+// A[i], i = 0, 1: opponent discs reachable from a P disc along direction i
+// through opponent discs only (board.py:124-139's "hostile" runs, seen from
+// P), exact: they come from the carry, and flips_col's carries rely on that.
+// G[i], i = 2..7: the Kogge-Stone fill from P along direction i: those runs
+// and P itself, G[i] = A_i | P.  A_i is never formed: P and O are disjoint and
+// the fill stays inside P | O, so A_i = G[i] & ~P, and both readers take that
+// in an operation they need anyway (the reach fold below, run_prefix).
 struct Position {
     u64 Oi, rOi;  // inner opponent discs, and bit-reversed
-    u64 A[8];
+    u64 rP;       // the mover's discs bit-reversed
+    u64 A[2];
+    u64 G[8];     // [0], [1] unused
     u64 reach;  // squares one step beyond an attached run (any content)
     u64 legal;  // Board.puttables as a mask (board.py:46-52) = reach & empty
 };
+
+// one direction's fill and its reach term: the squares one step beyond the run
+// A = G & ~P are sh(A) = sh(G) & ~sh(P) (a shift distributes over bitwise
+// logic; the zeros it brings in, and the bits that wrap round a file, are the
+// same in both terms), and sh(P) is the fill's own first temporary.  Folded
+// into the running OR as one v_bitop3_b32 per half: m | (sh(G) & ~PS).
+// Taken right after the fill, so that PS dies at once.
+template <int S, bool L>
+__device__ __forceinline__ u64 fill_reach(u64 P, const PairProp& q, u64& m) {
+    const Fill f = ks<S, L>(P, q);
+    m = bitop3<0xF4>(m, sh<S, L>(f.G), f.PS);
+    return f.G;
+}
 
 // ORDER: the order the six Kogge-Stone fills are written in (digits = the
 // direction pairs 7/8/9).  It only steers hipcc's register allocation: a
 // v_bitop3_b32 whose three sources sit in one VGPR bank issues in 4.3 cycles
 // instead of 2.5, and the bit pairs of 64-bit values make that likely; the
 // order with the fewest such instructions in each kernel's hot loop was picked
-// by tools/valu_mix.py (random rollout: 7-9-8, 11 -> 3 per ply).
-constexpr int kFillOrder = 798;
+// by tools/valu_mix.py.  Re-picked over the six orders with the reach terms
+// folded into the fills: 7-8-9 leaves the fewest in the random loop (14 per
+// two plies; 28-34 at the others), the greedy child loop (6; 8-10) and the
+// eval child loop (17; 19-21), and the least scratch in the 1-ply kernels.
+constexpr int kFillOrder = 789;
 template <int ORDER = kFillOrder>
 __device__ __forceinline__ void analyse(u64 P, u64 O, Position& s) {
     const u64 Oi = and2(O, INNER_FILES);
     s.Oi = Oi;
     s.rOi = rev64(Oi);
+    s.rP = rev64(P);
     // the horizontal pair needs no propagators (carry tricks below)
-    const PairProp v = pair_prop<8>(O), d9 = pair_prop<9>(Oi), d7 = pair_prop<7>(Oi);
     // east (+1): bits along the ray are contiguous, so one add propagates a
     // carry from each P disc through its adjacent run of inner opponent discs
     // and clears exactly those run bits: A = Oi & ~(Oi + (P << 1)).
     s.A[0] = east_run(P, Oi);
     // west (-1): the same on the bit-reversed board
-    s.A[1] = rev64(east_run(rev64(P), s.rOi));
-    // the Kogge-Stone fills from P stay inside P | O, so "minus P" is "and O"
+    s.A[1] = rev64(east_run(s.rP, s.rOi));
+    // a legal square is one step beyond an attached run, and empty
+    u64 m = or2(sh<1, true>(s.A[0]), sh<1, false>(s.A[1]));
+    // One direction pair at a time: its propagators, its two fills, their
+    // reach terms, then a scheduling barrier.  Left to itself hipcc interleaves
+    // the three pairs, with every pair's propagators and shifted sources live
+    // at once: the 1-ply kernels, at their VGPR ceilings, then spill 8-12 B
+    // more per lane than with the run sets kept (tests/test_codeobj.py's
+    // caps); pair by pair they spill less than before (greedy 48 -> 32 B,
+    // eval 16 -> 8 B).
     {
         constexpr int order[3] = {ORDER / 100, ORDER / 10 % 10, ORDER % 10};
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             if (order[k] == 8) {
-                s.A[2] = and2(ks<8, true>(P, v), O);
-                s.A[3] = and2(ks<8, false>(P, v), O);
+                const PairProp v = pair_prop<8>(O);
+                s.G[2] = fill_reach<8, true>(P, v, m);
+                s.G[3] = fill_reach<8, false>(P, v, m);
             } else if (order[k] == 9) {
-                s.A[4] = and2(ks<9, true>(P, d9), O);
-                s.A[5] = and2(ks<9, false>(P, d9), O);
+                const PairProp d9 = pair_prop<9>(Oi);
+                s.G[4] = fill_reach<9, true>(P, d9, m);
+                s.G[5] = fill_reach<9, false>(P, d9, m);
             } else {
-                s.A[6] = and2(ks<7, true>(P, d7), O);
-                s.A[7] = and2(ks<7, false>(P, d7), O);
+                const PairProp d7 = pair_prop<7>(Oi);
+                s.G[6] = fill_reach<7, true>(P, d7, m);
+                s.G[7] = fill_reach<7, false>(P, d7, m);
             }
+            __builtin_amdgcn_sched_barrier(0);
         }
     }
-    // a legal square is one step beyond an attached run, and empty
-    u64 m = or3(sh<1, true>(s.A[0]), sh<1, false>(s.A[1]), sh<8, true>(s.A[2]));
-    m = or3(m, sh<8, false>(s.A[3]), sh<9, true>(s.A[4]));
-    m = or3(m, sh<9, false>(s.A[5]), sh<7, true>(s.A[6]));
-    m = or2(m, sh<7, false>(s.A[7]));
     s.reach = m;
     s.legal = bitop3<0x04>(P, m, O);  // ~P & m & ~O: one v_bitop3_b32 per half
 }
@@ -224,6 +268,7 @@ __device__ __forceinline__ void analyse(u64 P, u64 O, Position& s) {
 // before the first square of R that is not in A:
 //     x = R & ~A;   flips = R & A & (x - 1)
 // (x != 0 whenever R & A != 0: an attached run ends in a P disc on the same ray).
+// The six table rays read the fill G = A | P and P in A's place (run_prefix).
 // Rays that leave in decreasing bit order use the same identity on the
 // bit-reversed board.  Table rows: 0..2 = rays +8, +9, +7 (normal order),
 // 3..5 = rays -8, -9, -7 stored bit-reversed; 64 squares each (3 KiB).
@@ -258,26 +303,50 @@ __device__ __forceinline__ void ray_table_init(u64* tab) {
 // the move's bit from the table (row kRayRows)
 __device__ __forceinline__ u64 square_bit(u32 sq, const u64* tab) { return tab[kRayRows * 64 + sq]; }
 __device__ __forceinline__ u64 and3(u64 a, u64 b, u64 c) { return bitop3<0x80>(a, b, c); }
-// For a ray R leaving the move in increasing bit order and the run set A of
-// the opposite direction, the flipped discs are the squares of R before R's
-// first square that is not in A: with x = R & ~A, R & A & (x - 1).  (x - 1)
-// sets the bits below x's lowest bit but keeps x's higher bits, so the "& A"
-// is needed.
-__device__ __forceinline__ u64 run_prefix(u64 R, u64 A) {
-    const u64 x = andn(R, A);
-    return and3(R, A, dec64(x));
+// For a ray R leaving the move in increasing bit order, the opposite
+// direction's fill G and the mover's discs P (run set A = G & ~P), the flipped
+// discs are the squares of R before R's first square that is not in A: with
+// x = R & ~A = R & (~G | P), one v_bitop3_b32 per half, they are
+// R & A & (x - 1).  (x - 1) sets the bits below x's lowest bit but keeps x's
+// higher bits, so an "&" with the runs is needed; it is taken with G, which is
+// at hand, not with A.  The result is therefore the flips plus, possibly, discs
+// of the mover's own further along the ray (squares of x above its lowest that
+// lie in G, hence in P).  place() ORs the flips into the mover's discs and
+// clears them from the opponent's, so own discs among them change neither
+// board; whoever counts or publishes flips must mask them with O first.
+__device__ __forceinline__ u64 run_prefix(u64 R, u64 G, u64 P) {
+    const u64 x = bitop3<0xB0>(R, G, P);  // R & (~G | P)
+    return and3(R, G, dec64(x));
 }
 
-// The run sets flips_rays reads, in the orientation it reads them: the runs
-// leaving a move in increasing bit order lie in A[1], A[3], A[5], A[7] (the
+// The run sets flips_col reads, in the orientation it reads them: the runs
+// leaving a move in increasing bit order lie in directions 1, 3, 5, 7 (the
 // opposite directions' runs, as analyse gives them), those leaving in
-// decreasing order in A[0], A[2], A[4], A[6], kept bit-reversed.  The 1-ply
-// policies build this once per parent and share it among its children.
-struct RunSets {
-    u64 A1, A3, A5, A7, rA0, rA2, rA4, rA6;
+// decreasing order in 0, 2, 4, 6, kept bit-reversed.  The horizontal pair as
+// exact run sets (A1, rA0), the six others as fills (G, rG), read together
+// with the mover's discs P and rP.
+// The 1-ply policies build this once per parent and share it among its
+// children; their LDS parent record holds the eight sets (Runs) next to P.
+// They are at their VGPR ceilings, and rP held across a parent's children
+// went to scratch (greedy: 20 B more per lane), so run_sets_parent takes the mover's discs out of the three reversed fills
+// once per parent (three 64-bit ANDs, which the reach fold saved): the exact
+// reversed runs in rG's place with rP = 0 make run_prefix the exact-run
+// identity, x = R & ~A, and the children's loop needs P alone.
+struct Runs {
+    u64 A1, G3, G5, G7, rA0, rG2, rG4, rG6;
 };
-__device__ __forceinline__ RunSets run_sets(const Position& s) {
-    return RunSets{s.A[1], s.A[3], s.A[5], s.A[7], rev64(s.A[0]), rev64(s.A[2]), rev64(s.A[4]), rev64(s.A[6])};
+struct RunSets {
+    Runs r;
+    u64 P, rP;
+};
+__device__ __forceinline__ RunSets run_sets(u64 P, const Position& s) {
+    return RunSets{{s.A[1], s.G[3], s.G[5], s.G[7], rev64(s.A[0]), rev64(s.G[2]), rev64(s.G[4]), rev64(s.G[6])},
+                   P, s.rP};
+}
+__device__ __forceinline__ RunSets run_sets_parent(u64 P, const Position& s) {
+    return RunSets{{s.A[1], s.G[3], s.G[5], s.G[7], rev64(s.A[0]), rev64(andn(s.G[2], P)), rev64(andn(s.G[4], P)),
+                    rev64(andn(s.G[6], P))},
+                   P, 0ull};
 }
 
 // The flips of the move at square sq (bit mv) in two parts, both including
@@ -289,21 +358,24 @@ __device__ __forceinline__ RunSets run_sets(const Position& s) {
 // empty move square on this side; A runs lie on the inner files, so the carry
 // never leaves the row): one add, as east_run, and the move's bit ORed in by
 // the same v_bitop3_b32.  West the same on the reversed board with A[0].  The
-// other six by the ray tables (run_prefix).  place() applies both parts: the
-// move's bit is never an opponent disc, so carrying it in the flips costs
-// nothing and saves the apply's separate OR.
+// other six by the ray tables (run_prefix), from the fills: they may carry
+// discs of the mover's own beyond a run's far end.  place() applies both
+// parts: neither the move's bit nor a disc of the mover's is an opponent disc,
+// so carrying them in the flips costs nothing, and the move's bit there saves
+// the apply's separate OR.  Not for counting flips: mask with O first.
 struct Flips {
     u64 f, fr;
 };
 // col = tab + sq: the move's column of the table (rows 64 entries apart)
-__device__ __forceinline__ Flips flips_col(u64 mv, const RunSets& r, const u64* col) {
+__device__ __forceinline__ Flips flips_col(u64 mv, const RunSets& s, const u64* col) {
+    const Runs& r = s.r;
     const u64 rmv = col[(kRayRows + 1) * 64];
     u64 f = bitop3<0xBA>(r.A1, lshl1_add(mv, r.A1), mv);     // (A1 & ~(A1 + (mv << 1))) | mv
     u64 fr = bitop3<0xBA>(r.rA0, lshl1_add(rmv, r.rA0), rmv);  // west, in reversed space
-    f = or3(f, run_prefix(col[0 * 64], r.A3), run_prefix(col[1 * 64], r.A5));
-    f = or2(f, run_prefix(col[2 * 64], r.A7));
-    fr = or3(fr, run_prefix(col[3 * 64], r.rA2), run_prefix(col[4 * 64], r.rA4));
-    fr = or2(fr, run_prefix(col[5 * 64], r.rA6));
+    f = or3(f, run_prefix(col[0 * 64], r.G3, s.P), run_prefix(col[1 * 64], r.G5, s.P));
+    f = or2(f, run_prefix(col[2 * 64], r.G7, s.P));
+    fr = or3(fr, run_prefix(col[3 * 64], r.rG2, s.rP), run_prefix(col[4 * 64], r.rG4, s.rP));
+    fr = or2(fr, run_prefix(col[5 * 64], r.rG6, s.rP));
     return Flips{f, rev64(fr)};
 }
 __device__ __forceinline__ Flips flips_rays(u32 sq, const RunSets& r, const u64* tab) {

@@ -136,9 +136,9 @@ __device__ __forceinline__ u32 child_key(u64 P, u64 O, const RunSets& s, u32 sq,
     int w[OTH_EVAL_FEATURES];
 #pragma unroll
     for (int j = 0; j < OTH_EVAL_FEATURES; j++) w[j] = row[j];
-    // |v| < 2^14; fill order 7-9-8 (bitboard.hpp analyse): 9 same-bank v_bitop3_b32 in
-    // this child loop against 13 at 8-7-9, +2-4% eval env-steps/s (tools/diag/r03_evalorder.sh)
-    const int v = eval_linear(w, P, moves<798>(P, O));
+    // |v| < 2^14; fill order 7-8-9 (bitboard.hpp analyse): 17 same-bank v_bitop3_b32 in
+    // this child loop against 19-21 at the five other orders (tools/valu_mix.py)
+    const int v = eval_linear(w, P, moves<789>(P, O));
     return ((u32)((1 << 20) - v) << 6) | sq;
 }
 
@@ -147,7 +147,7 @@ template <int POLICY>
 __device__ __forceinline__ u32 lane_choose(const Position& pos, u64 P, u64 O, const u64* rays, const int* w_tab) {
     u32 best = 0xFFFFFFFFu;
     u64 legal = pos.legal;
-    const RunSets s = run_sets(pos);
+    const RunSets s = run_sets_parent(P, pos);
     const int* row = child_row<POLICY>(P, O, w_tab);
     while (legal) {
         const u32 sq = (u32)__builtin_ctzll(legal);  // legal != 0
@@ -180,7 +180,7 @@ __device__ __forceinline__ u32 lane_choose(const Position& pos, u64 P, u64 O, co
 // without scoring its child cut greedy VALU by 0.9% but ran 1.3% (greedy) /
 // 5% (eval) slower per launch; tools/diag/r05_variants.patch.)
 struct CoopWave {
-    u64 rec[64][10];  // parent lane: P, O, its RunSets (8 words; A1's bit 0, a1, carries the eval table)
+    u64 rec[64][10];  // parent lane: P, O, its Runs (8 words; A1's bit 0, a1, carries the eval table)
     u64 legal[64];    // parent lane's legal mask (0: not choosing)
     u32 best[64];
 };
@@ -188,11 +188,15 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
-static_assert(sizeof(RunSets) == 8 * sizeof(u64), "parent record: P, O, RunSets");
+static_assert(sizeof(Runs) == 8 * sizeof(u64), "parent record: P, O, Runs");
+// the record carries run_sets_parent's sets (bitboard.hpp): the fills of the
+// increasing rays, read with P, and the exact reversed runs, read with rP = 0
 __device__ __forceinline__ void load_parent(const u64* r, u64& P, u64& O, RunSets& s) {
     P = r[0];
     O = r[1];
-    s = *reinterpret_cast<const RunSets*>(r + 2);
+    s.r = *reinterpret_cast<const Runs*>(r + 2);
+    s.P = P;
+    s.rP = 0;
 }
 // inclusive scan over the wave's 64 lanes (DPP row shifts, then the row
 // broadcasts of lanes 15 and 31)
@@ -218,9 +222,9 @@ __device__ u32 coop_choose(bool need, u64 P, u64 O, u32 tbl, const Position& pos
         u64* r = cw.rec[lane];
         r[0] = P;
         r[1] = O;
-        RunSets rs = run_sets(pos);  // reversed once per parent, not per child
+        Runs rs = run_sets_parent(P, pos).r;  // reversed once per parent, not per child
         if (POLICY == OTH_POLICY_EVAL) rs.A1 |= (u64)(tbl & 1u);
-        *reinterpret_cast<RunSets*>(r + 2) = rs;
+        *reinterpret_cast<Runs*>(r + 2) = rs;
     };
     // greedy (round 6): the record first, on either path, since the caller
     // plays the chosen move from it
@@ -263,7 +267,7 @@ __device__ u32 coop_choose(bool need, u64 P, u64 O, u32 tbl, const Position& pos
     const int* row = w_s;
     auto enter = [&](u32 q) {
         load_parent(cw.rec[q], Pp, Op, ps);
-        row = child_row<POLICY>(Pp, Op, w_s + ((ps.A1 & 1ull) ? kEvalTable : 0));
+        row = child_row<POLICY>(Pp, Op, w_s + ((ps.r.A1 & 1ull) ? kEvalTable : 0));
     };
     if (cnt_mine) {
         m = cw.legal[p];
@@ -748,7 +752,7 @@ __global__ __launch_bounds__(kBlock, rollout_waves_per_simd(POLICY)) void rollou
                 passed = false;
                 const u32 off = kth_bit_off(legal, rng.pick(nl), c_lo, kth_tab);
                 const u64* col = ray_col(rays, off);
-                const Flips f = flips_col(col[kRayRows * 64], run_sets(pos), col);
+                const Flips f = flips_col(col[kRayRows * 64], run_sets(X, pos), col);
                 if (RECORD) {
                     rec_put(npass, (uint8_t)(off >> 3));
                     npass++;
@@ -885,7 +889,7 @@ __global__ __launch_bounds__(kBlock, rollout_waves_per_simd(POLICY)) void rollou
                 // them in registers: the same change cost it 3.80 -> 3.97 ms
                 // (tools/gpu_greedy_ab.sh, profiles/r06_notes.md).
                 constexpr bool kFromRecord = POLICY == OTH_POLICY_GREEDY;
-                if (kFromRecord && moving && !choose) play(sq, run_sets(pos));
+                if (kFromRecord && moving && !choose) play(sq, run_sets_parent(P, pos));
                 if (__ballot(choose)) {  // wave-uniform: every lane of the wave joins
                     const u32 tbl = side == OTH_BLACK ? tbl_black : tbl_black ^ 1u;
                     const u32 c = coop_choose<POLICY>(choose, P, O, tbl, pos, cw, rays, w_s, kth_tab, (u32)lane,
@@ -900,7 +904,7 @@ __global__ __launch_bounds__(kBlock, rollout_waves_per_simd(POLICY)) void rollou
                         }
                     }
                 }
-                if (!kFromRecord && moving) play(sq, run_sets(pos));
+                if (!kFromRecord && moving) play(sq, run_sets_parent(P, pos));
             }
         }
         if constexpr (kRecStage) {  // the wave's records, one contiguous span, 16 bytes a lane
