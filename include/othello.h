@@ -20,10 +20,19 @@
  *
  * Ownership / errors / threading:
  *   - every pointer is DEVICE memory owned by the caller (e.g. torch tensors);
- *     the library keeps no device state (the rollouts' work counter is a
- *     word the caller passes in, see oth_rollout) and allocates nothing:
- *     the TD calls that need scratch (oth_td_sort_pairs, oth_td_lookup,
- *     oth_td_merge) take it from the caller, with a size query;
+ *     the library keeps no device state that a call's result depends on (the
+ *     rollouts' work counter is a word the caller passes in, see oth_rollout)
+ *     and allocates nothing per call: the TD calls that need scratch
+ *     (oth_td_sort_pairs, oth_td_lookup, oth_td_merge) take it from the
+ *     caller, with a size query.  The one exception: the first random-policy
+ *     oth_rollout from the standard opening (start == NULL, moves == NULL) on
+ *     a device allocates and builds that device's opening tree (7.5 MB, kept
+ *     for the process; a table of the first plies, which are the same for
+ *     every game), on a stream of its own that it waits for.  Not while
+ *     `stream` is capturing: such a launch, and the library for good if the
+ *     allocation fails, computes every ply instead, with the same results.
+ *     OTH_OPENING_DEPTH in the environment (0..8, read per launch; 0 = never
+ *     use or build the table) overrides the depth looked up;
  *   - calls are asynchronous on `stream` (a hipStream_t; NULL = default stream)
  *     and thread-safe on distinct streams; they may be captured in a hipGraph;
  *   - return value: OTH_OK (0), OTH_EINVAL (invalid argument, nothing launched),

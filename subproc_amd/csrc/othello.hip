@@ -32,6 +32,7 @@
 
 #include "../../include/othello.h"
 #include "bitboard.hpp"
+#include "opening_tree.hpp"
 #include "td_skey.hpp"
 
 #define OTH_VERSION "subproc_amd 0.1.0 gfx950"
@@ -551,6 +552,16 @@ struct RolloutArgs {
     // in the environment turns it off): a fresh batch hands its games over to
     // the wave's LDS pool once no more than handoff_k lanes are still playing
     u32 handoff_k;
+    // the random policy's opening walk (kernel without move records, games from
+    // the standard opening): the first open_depth plies of a fresh game are
+    // looked up in the device's opening tree (opening_tree.hpp); 0 = every ply
+    // is computed.  Wave-uniform, like the two table pointers.
+    u32 open_depth;
+    u32 open_lds_nodes;   // nodes of the upper levels every block copies to LDS
+    u32 open_lds_leaves;  // boards of the leaf level in LDS too (0: read from memory)
+    u32 open_leaf0;       // global index of the leaf level's first node
+    const u32* open_nodes;
+    const ulonglong2* open_boards;
 };
 
 // Batch-tail compaction (shipped since round 5 in the random-policy kernel
@@ -610,6 +621,17 @@ __global__ __launch_bounds__(kBlock, rollout_waves_per_simd(POLICY)) void rollou
     __shared__ CoopWave coop[POLICY == OTH_POLICY_RANDOM ? 1 : kBlock / 64];
     constexpr bool kPool = POLICY == OTH_POLICY_RANDOM && !RECORD && !RUNNER;
     __shared__ Parked pool_s[kPool ? kBlock / 64 : 1][kPool ? kPoolCap : 1];
+    // kPool: the block's copy of the opening tree's upper part (dynamic LDS,
+    // sized by the launch: opening_lds_bytes): the leaf level's boards when the
+    // depth is at most kOpeningLdsLeafDepth, then the nodes above
+    extern __shared__ ulonglong2 open_dyn[];
+    ulonglong2* const open_leaf_s = open_dyn;
+    u32* const open_s = reinterpret_cast<u32*>(open_dyn + (kPool ? a.open_lds_leaves : 0u));
+    if (kPool && a.open_depth) {
+        for (u32 k = threadIdx.x; k < a.open_lds_leaves; k += kBlock)
+            open_leaf_s[k] = a.open_boards[a.open_leaf0 + k];
+        for (u32 k = threadIdx.x; k < a.open_lds_nodes; k += kBlock) open_s[k] = a.open_nodes[k];
+    }
     for (int k = threadIdx.x; k < OTH_HIST_BINS; k += kBlock) hist_s[k] = 0;
     kth_table_init(kth_tab);
     ray_table_init(rays);
@@ -717,6 +739,34 @@ __global__ __launch_bounds__(kBlock, rollout_waves_per_simd(POLICY)) void rollou
                     npass = e.bits >> 9;
                 }
                 parked -= take;
+            }
+            if constexpr (kPool) {
+                // the opening walk: the position after open_depth plies from the
+                // path of the game's own draws.  No pass occurs inside the tree,
+                // so the side to move is Black after an even number of plies;
+                // discs0 stays the opening's count, so the looked-up placements
+                // count as env-steps.  Parked games have walked already.  The
+                // upper levels (at the shipped depth, all of them and the leaf)
+                // come from the block's LDS copy: a dependent read from memory
+                // here costs more than the plies it saves.
+                const u32 depth = __builtin_amdgcn_readfirstlane(from_pool ? 0u : a.open_depth);
+                if (depth && active) {
+                    u32 node = 0;
+                    const u32 in_lds = min(depth, (u32)kOpeningLdsDepth);
+                    for (u32 d = 0; d < in_lds; d++) {
+                        const u32 e = open_s[node];
+                        node = (e >> kOpeningNlBits) + rng.pick(e & kOpeningNlMask);
+                    }
+                    for (u32 d = in_lds; d < depth; d++) {
+                        const u32 e = a.open_nodes[node];
+                        node = (e >> kOpeningNlBits) + rng.pick(e & kOpeningNlMask);
+                    }
+                    const ulonglong2 leaf =
+                        a.open_lds_leaves ? open_leaf_s[node - a.open_leaf0] : a.open_boards[node];
+                    P = leaf.x;
+                    O = leaf.y;
+                    b0 = !(depth & 1u);
+                }
             }
             const u32 hand_k = __builtin_amdgcn_readfirstlane(kPool && !from_pool ? a.handoff_k : 0u);
             const u32 parked0 = __builtin_amdgcn_readfirstlane(parked);
@@ -2164,8 +2214,10 @@ int env_int(const char* name, int dflt) {
     return v && *v ? atoi(v) : dflt;
 }
 
-// per-device launch geometry (a process may drive several GPUs), resolved on
-// first use; the only state the library keeps, and none of it on the device
+// per-device state (a process may drive several GPUs), resolved on first use:
+// the launch geometry, and the one thing the library keeps on the device, the
+// random rollout's opening tree (opening_tree.hpp; < 8 MB, built on the first
+// random-policy rollout from the standard opening, kept for the process)
 constexpr int kMaxDevices = 64;
 constexpr int kMaxBlocksPerCu = 5;
 constexpr int kRandomBlocksPerCu = 3;
@@ -2173,9 +2225,51 @@ constexpr int64_t kBigLaunch = 1 << 22;  // games: a launch this large amortises
 struct DeviceState {
     std::atomic<int> ready{0};
     Tuning tuning;
+    std::atomic<void*> tree{nullptr};  // the built opening tree (published with release ordering)
+    bool tree_failed = false;          // under g_dev_mu: allocation or build failed, depth 0 from now on
 };
 DeviceState g_dev[kMaxDevices];
 std::mutex g_dev_mu;
+
+// The shipped depth of the opening walk (env OTH_OPENING_DEPTH, 0..8; 0 = off).
+// Chosen by measurement: the deepest walk that reads nothing
+// from memory; 6 and 8 remove more instructions and gain less or lose.
+constexpr int kOpeningDepth = 4;
+
+// The device's opening tree, built on first use: under g_dev_mu, on a stream of
+// its own, waiting for that stream only.  nullptr (the launch then computes
+// every ply) while the caller's stream is capturing -- no allocation, launch
+// or synchronise may happen during a capture; a later eager launch builds it --
+// and for good once allocation or the build has failed.
+void* opening_tree(DeviceState& d, hipStream_t caller) {
+    if (void* t = d.tree.load(std::memory_order_acquire)) return t;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(caller, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lock(g_dev_mu);
+    if (void* t = d.tree.load(std::memory_order_relaxed)) return t;
+    if (d.tree_failed) return nullptr;
+    void* base = nullptr;
+    hipStream_t s = nullptr;
+    bool ok = hipMalloc(&base, kOpeningBytes) == hipSuccess;
+    if (ok) {
+        ok = hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess;
+        if (ok) {
+            ok = opening_tree_build(base, OPEN_BLACK, OPEN_WHITE, s);
+            (void)hipStreamDestroy(s);
+        }
+        if (!ok) (void)hipFree(base);
+    }
+    (void)hipGetLastError();
+    if (!ok) {
+        d.tree_failed = true;
+        return nullptr;
+    }
+    d.tree.store(base, std::memory_order_release);
+    return base;
+}
 
 DeviceState* device_state() {
     int dev = 0;
@@ -2322,6 +2416,27 @@ int rollout_launch(const uint64_t* start, const uint8_t* start_turn, uint64_t se
                       ? (u32)std::min(std::max(env_int("OTH_HANDOFF_K", (int)kHandoffK), 0), (int)kHandoffKMax)
                       : 0u;
     hipStream_t st = (hipStream_t)stream;
+    // the opening walk: the random kernel without move records, games from the
+    // standard opening (OTH_OPENING_DEPTH=0 turns it off, like a tree not built)
+    a.open_depth = a.open_lds_nodes = a.open_lds_leaves = a.open_leaf0 = 0u;
+    size_t open_lds = 0;
+    a.open_nodes = nullptr;
+    a.open_boards = nullptr;
+    if (policy == OTH_POLICY_RANDOM && !run && !moves && !start) {
+        const int depth = std::min(std::max(env_int("OTH_OPENING_DEPTH", kOpeningDepth), 0), kOpeningDepthMax);
+        if (depth > 0) {
+            if (void* base = opening_tree(*ds, st)) {
+                const OpeningTree tree = opening_tree_at(base);
+                a.open_depth = (u32)depth;
+                a.open_lds_nodes = opening_off(std::min(depth, kOpeningLdsDepth));
+                a.open_lds_leaves = depth <= kOpeningLdsLeafDepth ? kOpeningLevel[depth] : 0u;
+                a.open_leaf0 = opening_off(depth);
+                open_lds = opening_lds_bytes(depth);
+                a.open_nodes = tree.nodes;
+                a.open_boards = tree.boards;
+            }
+        }
+    }
     if (run) {
         if (policy == OTH_POLICY_EVAL) {
             if (moves) rollout_kernel<OTH_POLICY_EVAL, true, true><<<grid, kBlock, 0, st>>>(a);
@@ -2339,7 +2454,7 @@ int rollout_launch(const uint64_t* start, const uint8_t* start_turn, uint64_t se
     } else {
         if (moves)
             rollout_kernel<OTH_POLICY_RANDOM, true><<<grid, kBlock, rec_stage_bytes(OTH_POLICY_RANDOM, true), st>>>(a);
-        else rollout_kernel<OTH_POLICY_RANDOM, false><<<grid, kBlock, 0, st>>>(a);
+        else rollout_kernel<OTH_POLICY_RANDOM, false><<<grid, kBlock, open_lds, st>>>(a);
     }
     return launched();
 }
