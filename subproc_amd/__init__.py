@@ -2,12 +2,14 @@
 path of ysnrkdm/subproc, re-designed for gfx950).
 
 Modules:
-  ops     tensor-level batched kernels (reset / legal / step / result / rollout)
+  ops     tensor-level batched kernels (reset / legal / step / result / rollout / solve)
   env     VecEnv: reset / legal_moves / step / result over N games in HBM
   board   drop-in ``board`` module: the reference Board class API
   codec   Edax move strings and book text (host side)
   dist    one-process-per-GPU sharded rollouts + histogram all-reduce
-The compute lives in lib/libsubproc_amd_hip.so (C-ABI: include/othello.h).
+The compute lives in lib/libsubproc_amd_hip.so (C-ABI: include/othello.h and,
+for the endgame solver, include/othello_solve.h).  ``solve`` / ``SolveResult``
+are ops.solve and its result type.
 """
 __version__ = "0.1.0"
 
@@ -15,4 +17,13 @@ from ._lib import (BLACK, HIST_BINS, PASS, WHITE, OthelloCallError, OthelloLibra
                    version as library_version)
 
 __all__ = ["BLACK", "WHITE", "PASS", "HIST_BINS", "OthelloLibraryError", "OthelloCallError", "load_library",
-           "library_version", "__version__"]
+           "library_version", "solve", "SolveResult", "__version__"]
+
+
+def __getattr__(name):
+    # ops imports torch: bound on first use, so that `import subproc_amd` stays light
+    if name in ("solve", "SolveResult"):
+        from . import ops
+
+        return getattr(ops, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

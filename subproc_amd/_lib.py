@@ -9,6 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsubproc_amd_hip.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello.h")
+SOLVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -25,6 +26,10 @@ TD_SKEY_BITS = 36         # include/othello.h packed update words: the sort key'
 TD_PACK_TURN_SHIFT = 36
 TD_PACK_VALUE_SHIFT = 56
 TD_FIT_BLOCKS, TD_FIT_COLS = 1024, 64
+SOLVE_MAX_EMPTIES = 12    # include/othello_solve.h
+SOLVE_SKIPPED, SOLVE_SOLVED, SOLVE_INVALID, SOLVE_LIMIT = 0, 1, 2, 3
+SOLVE_NO_MOVE = 255
+SOLVE_DEFAULT_NODE_LIMIT = 1 << 28
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -69,6 +74,12 @@ SIGNATURES = {
     "oth_td_fit_moments": (_I, [_P, _P, _I64, _P, _P, _P]),
 }
 
+# the endgame solver, include/othello_solve.h (no host twin: its own prefix)
+SOLVE_SIGNATURES = {
+    "oths_solve": (_I, [_P, _P, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _I64, _P]),
+    "oths_solve_grid": (_I, [_I64]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -99,7 +110,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise OthelloLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -1,0 +1,221 @@
+// solve.hip — exact endgame solver for gfx950: batched perfect-play search, one
+// lane per position (include/othello_solve.h).
+//
+// The search itself is solve_core.hpp's advance(): one step of one position's
+// alpha-beta per loop iteration, so the 64 lanes of a wave, each somewhere in
+// its own tree, execute the same instructions.  This file gives it
+//   * the rules: bitboard.hpp's moves() and flips_carry(), the ones the step
+//     kernel plays by (no second statement of the rules);
+//   * the stack: an LDS array indexed [depth][field][lane] in 32-bit words, so
+//     a wave's access is one word per bank whatever depth each lane is at.
+//     No per-thread array, no recursion: the kernel uses no scratch;
+//   * the refill: a lane whose position ends takes the next one from the
+//     caller's work word.  The wave's idle lanes are counted by one ballot per
+//     iteration; once kRefillMin of them wait (or nothing else is left to do)
+//     they are served by ONE atomic of lane 0 (their count added), each taking
+//     the slot of its rank.  Every lane makes exactly one failing request, so
+//     the requests of a launch add up to n + lanes; the add that reaches that
+//     sum resets the word to 0 (oth_rollout's contract).  Measured (DESIGN.md
+//     §12, 1M positions at 6 empties / 524k at 8, full grid): refilling each
+//     lane at once 12.4 / 47.9 ms (the one work word saturates: an atomic per
+//     wave nearly every iteration), at 8 idle lanes 4.7 / 48.4 ms, a whole
+//     wave at a time like the rollouts 8.9 / 84.4 ms.
+//
+// Geometry: one wave per block.  11 frames x 28 B x 64 lanes = 19.25 KB of LDS
+// per block, eight blocks in a CU's 160 KB: two waves per SIMD, which this
+// dependent VALU chain wants (a 256-thread block would be alone on its CU, one
+// wave per SIMD).  The waves share nothing, so there is no barrier.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <atomic>
+
+#include "../../include/othello.h"
+#include "../../include/othello_solve.h"
+#include "bitboard.hpp"
+#include "solve_core.hpp"
+
+static_assert(OTHS_MAX_EMPTIES == oths::kMaxEmpties, "header and core disagree");
+static_assert(OTHS_SKIPPED == oths::kSkipped && OTHS_SOLVED == oths::kSolved && OTHS_INVALID == oths::kInvalid &&
+                  OTHS_LIMIT == oths::kLimit && OTHS_NO_MOVE == oths::kNoMove && OTH_PASS == oths::kPassMove,
+              "header and core disagree");
+
+namespace {
+
+using oths::u32;
+using oths::u64;
+
+constexpr int kSolveBlock = 64;  // one wave
+constexpr int kRefillMin = 8;    // idle lanes that make a wave refill (see above)
+
+struct DeviceRules {
+    static __device__ __forceinline__ u64 moves(u64 P, u64 O) { return oth::moves(P, O); }
+    static __device__ __forceinline__ u64 flips(u32 sq, u64 P, u64 O) { return oth::flips_carry(sq, P, O); }
+    static __device__ __forceinline__ u32 lowest(u64 m) { return (u32)__builtin_ctzll(m); }
+    static __device__ __forceinline__ int count(u64 x) { return __popcll(x); }
+};
+
+// frames [depth][field][lane]; `base` already points at the lane's column
+struct LdsStack {
+    u32* base;
+    __device__ __forceinline__ u32* at(int depth) const { return base + depth * (oths::kFields * kSolveBlock); }
+    __device__ __forceinline__ void store(int depth, u64 P, u64 O, u64 M, u32 w) {
+        u32* f = at(depth);
+        f[0 * kSolveBlock] = (u32)P;
+        f[1 * kSolveBlock] = (u32)(P >> 32);
+        f[2 * kSolveBlock] = (u32)O;
+        f[3 * kSolveBlock] = (u32)(O >> 32);
+        f[4 * kSolveBlock] = (u32)M;
+        f[5 * kSolveBlock] = (u32)(M >> 32);
+        f[6 * kSolveBlock] = w;
+    }
+    __device__ __forceinline__ void load(int depth, u64& P, u64& O, u64& M, u32& w) const {
+        const u32* f = at(depth);
+        P = (u64)f[0 * kSolveBlock] | ((u64)f[1 * kSolveBlock] << 32);
+        O = (u64)f[2 * kSolveBlock] | ((u64)f[3 * kSolveBlock] << 32);
+        M = (u64)f[4 * kSolveBlock] | ((u64)f[5 * kSolveBlock] << 32);
+        w = f[6 * kSolveBlock];
+    }
+};
+
+struct SolveArgs {
+    const u64* boards;
+    const uint8_t* turn;
+    int8_t* value;
+    uint8_t* best_move;
+    uint8_t* status;
+    u32* nodes;
+    unsigned long long* work;
+    u64 n;
+    u64 total;  // n + lanes of the grid: what the launch's requests add up to
+    u32 limit;
+    int max_empties;
+    int refill_min;  // idle lanes that make a wave refill (1: each lane at once .. 64: the rollouts' batch dequeue)
+};
+
+__device__ __forceinline__ void emit(const SolveArgs& a, u64 i, int value, u32 mv, u32 status, u32 nodes) {
+    if (a.value) a.value[i] = (int8_t)value;
+    if (a.best_move) a.best_move[i] = (uint8_t)mv;
+    if (a.status) a.status[i] = (uint8_t)status;
+    if (a.nodes) a.nodes[i] = nodes;
+}
+
+__global__ __launch_bounds__(kSolveBlock) void solve_kernel(SolveArgs a) {
+    __shared__ u32 frames[oths::kFrames * oths::kFields * kSolveBlock];
+    const u32 lane = threadIdx.x;
+    LdsStack stk{frames + lane};
+    oths::Lane L;
+    L.depth = -1;
+    u64 idx = 0;
+    bool exhausted = false;  // the lane has made its failing request
+    for (;;) {
+        const bool idle = L.depth < 0;
+        const bool want = idle && !exhausted;
+        const u64 wantm = __ballot(want);
+        const u64 busym = __ballot(!idle);
+        if ((wantm | busym) == 0) break;
+        const u64 cnt = (u64)__popcll(wantm);
+        if (wantm != 0 && ((int)cnt >= a.refill_min || busym == 0)) {
+            u64 base = 0;
+            if (lane == 0) {
+                base = atomicAdd(a.work, cnt);
+                if (base + cnt == a.total) atomicExch(a.work, 0ull);  // every request is made: reset
+            }
+            base = __shfl(base, 0);
+            if (want) {
+                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
+                if (g >= a.n) {
+                    exhausted = true;
+                } else {
+                    const ulonglong2 b = reinterpret_cast<const ulonglong2*>(a.boards)[g];
+                    const bool white = a.turn && a.turn[g] == OTH_WHITE;
+                    const u32 st = oths::classify(b.x, b.y, 64 - __popcll(b.x | b.y), a.max_empties);
+                    if (st == oths::kSolved) {
+                        oths::start(L, white ? b.y : b.x, white ? b.x : b.y);
+                        idx = g;
+                    } else {
+                        emit(a, g, 0, oths::kNoMove, st, 0u);
+                    }
+                }
+            }
+        }
+        if (L.depth >= 0) {
+            oths::advance<DeviceRules>(L, stk, a.limit);
+            if (L.depth < 0) emit(a, idx, L.value, L.best_mv, L.status, L.nodes);
+        }
+    }
+}
+
+inline int status_of(hipError_t e) { return e == hipSuccess ? OTH_OK : -(int)e; }
+
+int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v && *v ? atoi(v) : dflt;
+}
+
+// blocks of the solve kernel a device holds at once, resolved on first use
+constexpr int kMaxDevices = 64;
+std::atomic<int> g_resident[kMaxDevices];
+
+int resident_blocks() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= kMaxDevices) return -1;
+    int r = g_resident[dev].load(std::memory_order_acquire);
+    if (r > 0) return r;
+    int cus = 256, per_cu = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(solve_kernel),
+                                                       kSolveBlock, 0);
+    (void)hipGetLastError();
+    r = std::max(cus, 1) * (per_cu > 0 ? per_cu : 4);
+    g_resident[dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
+    return r;
+}
+
+int solve_grid(int64_t n) {
+    const int resident = resident_blocks();
+    if (resident <= 0) return -1;
+    const int cap = std::min(std::max(env_int("OTH_SOLVE_BLOCKS", resident), 1), resident);
+    return (int)std::min<int64_t>((n + kSolveBlock - 1) / kSolveBlock, (int64_t)cap);
+}
+
+}  // namespace
+
+extern "C" {
+
+int oths_solve(const uint64_t* boards, const uint8_t* turn, int max_empties, uint32_t node_limit, int8_t* value,
+               uint8_t* best_move, uint8_t* status, uint32_t* nodes, uint64_t* work, int64_t n, void* stream) {
+    if (n < 0 || !work || max_empties < 0 || max_empties > OTHS_MAX_EMPTIES || (n > 0 && !boards)) return OTH_EINVAL;
+    if (n == 0) return OTH_OK;
+    const int grid = solve_grid(n);
+    if (grid <= 0) return status_of(hipErrorInvalidDevice);
+    SolveArgs a;
+    a.boards = boards;
+    a.turn = turn;
+    a.value = value;
+    a.best_move = best_move;
+    a.status = status;
+    a.nodes = nodes;
+    a.work = reinterpret_cast<unsigned long long*>(work);
+    a.n = (u64)n;
+    a.total = (u64)n + (u64)grid * kSolveBlock;
+    a.limit = node_limit ? node_limit : OTHS_DEFAULT_NODE_LIMIT;
+    a.max_empties = max_empties;
+    // OTH_SOLVE_REFILL=1..64 (tools/solve_bench.py's A/B): the idle lanes that
+    // make a wave refill; 64 is the rollouts' batch dequeue
+    a.refill_min = std::min(std::max(env_int("OTH_SOLVE_REFILL", kRefillMin), 1), kSolveBlock);
+    solve_kernel<<<(unsigned)grid, kSolveBlock, 0, (hipStream_t)stream>>>(a);
+    return status_of(hipGetLastError());
+}
+
+int oths_solve_grid(int64_t n) {
+    if (n < 0) return OTH_EINVAL;
+    if (n == 0) return 0;
+    const int grid = solve_grid(n);
+    return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
+}
+
+}  // extern "C"

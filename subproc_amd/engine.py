@@ -28,6 +28,10 @@ to the first move in puttables order) or "eval" (maximise the mover's linear
 eval of the child under an eval table, ties likewise -- the kernels' eval
 policy).  ``--params FILE`` loads the table from the file paramgen.py writes
 (paramgen.py:12-19), the file the reference's own engines read.
+``--solve-empties K`` (K = 1..12) plays the endgame perfectly, as the engines
+this one stands in for do: with at most K empty squares and a legal move, the
+move is the exact solver's (ops.solve: best final disc difference, ties to the
+lowest square), whatever the policy.
 """
 import argparse
 import random
@@ -37,12 +41,15 @@ import numpy as np
 import torch
 
 from . import board as gboard
-from . import ops, params
+from . import _lib, ops, params
 from .codec import handstr_from_coord
 
 
 class Engine:
-    def __init__(self, name="GPU", policy="greedy", seed=0, weights=None):
+    def __init__(self, name="GPU", policy="greedy", seed=0, weights=None, solve_empties=0):
+        if not 0 <= solve_empties <= _lib.SOLVE_MAX_EMPTIES:
+            raise ValueError(f"solve_empties must lie in 0..{_lib.SOLVE_MAX_EMPTIES}")
+        self.solve_empties = solve_empties
         self.name = name
         self.policy = policy
         self.rng = random.Random(seed)
@@ -77,11 +84,33 @@ class Engine:
         k = min(range(len(puts)), key=lambda i: (mob[i], i))  # ties -> lowest square
         return handstr_from_coord(*puts[k])
 
+    def _choose_solved(self):
+        """The solver's move for the side to move (one oths_solve launch), or
+        None when it gives none (more than solve_empties empties)."""
+        b = self.board
+        bl, wh = b.bitboards()
+        if 64 - bin(bl | wh).count("1") > self.solve_empties:
+            return None
+        dev = torch.device("cuda", torch.cuda.current_device())
+        boards = ops.from_numpy_u64(np.array([[bl, wh]], np.uint64), dev)
+        side = torch.full((1,), b.turn, dtype=torch.uint8, device=dev)
+        # (a position that would need more than 2**24 nodes -- none at <= 12
+        # empties in DESIGN.md §12's samples -- falls back to the policy)
+        r = ops.solve(boards, side, max_empties=self.solve_empties, node_limit=1 << 24)
+        sq = int(r.best_move.cpu()[0])
+        if int(r.status.cpu()[0]) != _lib.SOLVE_SOLVED or sq > 63:
+            return None
+        return handstr_from_coord(sq & 7, sq >> 3)
+
     def choose(self):
         b = self.board
         puts = b.puttables(b.turn)
         if not puts:
             return "PS"
+        if self.solve_empties > 0 and b.turn in (gboard.Black, gboard.White):
+            mv = self._choose_solved()
+            if mv is not None:
+                return mv
         if self.policy == "random":
             x, y = puts[self.rng.randrange(len(puts))]
             return handstr_from_coord(x, y)
@@ -103,6 +132,8 @@ class Engine:
             out("")
         elif cmd == "verbose p":
             extra = " weights=%s" % self.weights.reshape(-1).tolist() if self.policy == "eval" else ""
+            if self.solve_empties > 0:
+                extra += " solve_empties=%d" % self.solve_empties
             out("%s policy=%s%s" % (self.name, self.policy, extra))
         elif cmd == "verbose 1":
             b = self.board
@@ -138,9 +169,11 @@ def main(argv=None):
     p.add_argument("--policy", choices=["random", "greedy", "eval"], default="greedy")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--params", default=None, help="eval table in the paramgen.py file format (policy eval)")
+    p.add_argument("--solve-empties", type=int, default=0, metavar="K",
+                   help="play the exact solver's move once at most K squares are empty (0 = never, max 12)")
     a = p.parse_args(argv)
     weights = params.read_paramgen(a.params)[1] if a.params else None
-    eng = Engine(a.name, a.policy, a.seed, weights)
+    eng = Engine(a.name, a.policy, a.seed, weights, a.solve_empties)
 
     def out(s):
         sys.stdout.write(s + "\n")

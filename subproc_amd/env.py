@@ -62,6 +62,12 @@ class VecEnv:
     def is_game_over(self):
         return ops.result(self.boards).terminal.bool()
 
+    def solve(self, max_empties=12, node_limit=0):
+        """Exact endgame solve of the current state (ops.solve): per game the
+        disc difference under perfect play from the mover's side and the move
+        that achieves it, for the games with at most `max_empties` empties."""
+        return ops.solve(self.boards, self.turn, max_empties=max_empties, node_limit=node_limit)
+
     def books(self):
         """Book text (serialize_str, board.py:214-221) of every game: oth_book_text
         on the device, one 67-byte line per game, decoded on the host."""

@@ -408,6 +408,55 @@ def rollout_runner(n, seed, game_id0=0, policy="eval", weights_a=None, weights_b
     return RunnerResult(fb, df, pl, mv, hist, ab)
 
 
+SolveResult = namedtuple("SolveResult", "value best_move status nodes")
+
+
+def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=None):
+    """Exact endgame solve (oths_solve, include/othello_solve.h): for every
+    position with at most ``max_empties`` (0..12) empty squares, the final disc
+    difference under perfect play by both sides, from the mover's side (White
+    if turn == 2, else Black; no bonus for empty squares), and the move that
+    achieves it.
+
+    Returns SolveResult(value int8, best_move uint8, status uint8, nodes):
+    best_move is the lowest square among the best moves, 64 for a forced pass,
+    255 when the game is over; status is _lib.SOLVE_SOLVED, SOLVE_SKIPPED (more
+    empties: value 0, best_move 255), SOLVE_INVALID (black & white overlap) or
+    SOLVE_LIMIT (the search of this position would have passed ``node_limit``
+    moves and passes; 0 = the library's default, 2**28).  ``nodes`` (uint32 as
+    int32 bits, with ``want_nodes``) is each position's count, else None.
+
+    ``work`` as in :func:`rollout`: default the current stream's
+    :func:`work_word` (shared with the rollouts), required under graph capture.
+    """
+    n = _n(boards)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if work is None and capturing:
+        raise RuntimeError("ops.solve under graph capture needs an explicit work word: an int64 (1,) device "
+                           "tensor zeroed before the capture, one per captured launch")
+    if not 0 <= int(node_limit) < 2**32:
+        raise ValueError("node_limit must fit 32 bits")
+    d = boards.device
+    pb = _dev(boards, "boards", torch.int64)
+    pt = _dev(turn, "turn", torch.uint8, (n,), d)
+    val = torch.empty(n, dtype=torch.int8, device=d)
+    mv = torch.empty(n, dtype=torch.uint8, device=d)
+    st = torch.empty(n, dtype=torch.uint8, device=d)
+    nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
+    w = work_word(d) if work is None else work
+    pw = _dev(w, "work", torch.int64, (1,), d)
+    with torch.cuda.device(d):
+        rc = _lib.load().oths_solve(pb, pt, int(max_empties), int(node_limit), val.data_ptr(), mv.data_ptr(),
+                                    st.data_ptr(), None if nd is None else nd.data_ptr(), pw, n, _stream())
+        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
+            if work is None:
+                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
+            elif not capturing:
+                w.zero_()
+        check(rc, "oths_solve")
+    return SolveResult(val, mv, st, nd)
+
+
 def sample_midgame(n, seed, index0=0, device="cuda"):
     """Synthetic reachable mid-game positions + one random legal move each (config 2 inputs)."""
     d = _device(device)
@@ -548,6 +597,6 @@ def from_numpy_u64(a, device="cuda"):
     return torch.from_numpy(a.view(np.int64).copy()).to(device)
 
 
-__all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", "sample_midgame", "replay",
+__all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", "solve", "sample_midgame", "replay",
            "book_text", "features", "evaluate", "to_numpy_u64", "from_numpy_u64",
            "StepResult", "Result", "RolloutResult", "Positions", "Replay", "BLACK", "WHITE", "PASS", "HIST_BINS"]
