@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libsubproc_amd_hip.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello.h")
 SOLVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve.h")
+SEARCH_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_search.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -30,6 +31,11 @@ SOLVE_MAX_EMPTIES = 12    # include/othello_solve.h
 SOLVE_SKIPPED, SOLVE_SOLVED, SOLVE_INVALID, SOLVE_LIMIT = 0, 1, 2, 3
 SOLVE_NO_MOVE = 255
 SOLVE_DEFAULT_NODE_LIMIT = 1 << 28
+SEARCH_MAX_DEPTH = 8      # include/othello_search.h
+SEARCH_TERMINAL_SCALE = 1 << 17
+SEARCH_SEARCHED, SEARCH_INVALID, SEARCH_LIMIT = 1, 2, 3
+SEARCH_NO_MOVE = 255
+SEARCH_DEFAULT_NODE_LIMIT = 1 << 28
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -80,6 +86,12 @@ SOLVE_SIGNATURES = {
     "oths_solve_grid": (_I, [_I64]),
 }
 
+# the depth-limited search, include/othello_search.h (its own prefix likewise)
+SEARCH_SIGNATURES = {
+    "othm_search": (_I, [_P, _P, _I, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _I64, _P]),
+    "othm_search_grid": (_I, [_I64]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -110,7 +122,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise OthelloLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

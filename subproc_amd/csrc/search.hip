@@ -1,0 +1,224 @@
+// search.hip — depth-limited alpha-beta search with the learner's eval at the
+// horizon, for gfx950: one lane per position (include/othello_search.h).
+//
+// The search itself is search_core.hpp's advance(): the solver's one-step
+// state machine with a depth horizon.  This file gives it what solve.hip gives
+// the solver's, in the same shape:
+//   * the rules: bitboard.hpp's moves() and flips_carry();
+//   * the stack: an LDS array indexed [depth][field][lane] in 32-bit words (one
+//     word per bank whatever depth each lane is at); no per-thread array, no
+//     recursion, no scratch;
+//   * the eval table: oth_eval's int8 [4][9], passed by value with the launch
+//     and widened into LDS (int rows padded to 12) by the block's one wave;
+//   * the refill: idle lanes take the next positions from the caller's work
+//     word, kRefillMin of them at a time by one atomic of lane 0, exactly as
+//     solve.hip does (its header has the contract and the measurement behind
+//     the 8).
+//
+// Geometry: one wave per block.  7 frames x 36 B x 64 lanes + the table =
+// 15.9 KB of LDS per block, eight blocks in a CU's 160 KB (two waves per
+// SIMD).  The waves share nothing; the one barrier orders the table's fill.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <atomic>
+
+#include "../../include/othello.h"
+#include "../../include/othello_search.h"
+#include "bitboard.hpp"
+#include "search_core.hpp"
+
+static_assert(OTHM_MAX_DEPTH == othm::kMaxDepth && OTHM_TERMINAL_SCALE == othm::kTerminal, "header and core disagree");
+static_assert(OTHM_SEARCHED == othm::kSearched && OTHM_INVALID == othm::kInvalid && OTHM_LIMIT == othm::kLimit &&
+                  OTHM_NO_MOVE == othm::kNoMove && OTH_PASS == othm::kPassMove,
+              "header and core disagree");
+static_assert(OTH_EVAL_PHASES == othm::kEvalPhases && OTH_EVAL_FEATURES == othm::kEvalFeatures &&
+                  OTH_EVAL_WEIGHTS == othm::kEvalPhases * othm::kEvalFeatures,
+              "the eval table's shape");
+
+namespace {
+
+using othm::u32;
+using othm::u64;
+
+constexpr int kSearchBlock = 64;  // one wave
+constexpr int kRefillMin = 8;     // idle lanes that make a wave refill (solve.hip's measurement)
+
+struct DeviceRules {
+    static __device__ __forceinline__ u64 moves(u64 P, u64 O) { return oth::moves(P, O); }
+    static __device__ __forceinline__ u64 flips(u32 sq, u64 P, u64 O) { return oth::flips_carry(sq, P, O); }
+    static __device__ __forceinline__ u32 lowest(u64 m) { return (u32)__builtin_ctzll(m); }
+    static __device__ __forceinline__ int count(u64 x) { return __popcll(x); }
+    // int8 weight x count <= 64: exact in 24 bits, a full-rate multiply
+    static __device__ __forceinline__ int mul(int w, int c) { return __mul24(w, c); }
+};
+
+// frames [depth][field][lane]; `base` already points at the lane's column
+struct LdsStack {
+    u32* base;
+    __device__ __forceinline__ u32* at(int depth) const { return base + depth * (othm::kFields * kSearchBlock); }
+    __device__ __forceinline__ void store(int depth, u64 P, u64 O, u64 M, int alpha, int beta, u32 w) {
+        u32* f = at(depth);
+        f[0 * kSearchBlock] = (u32)P;
+        f[1 * kSearchBlock] = (u32)(P >> 32);
+        f[2 * kSearchBlock] = (u32)O;
+        f[3 * kSearchBlock] = (u32)(O >> 32);
+        f[4 * kSearchBlock] = (u32)M;
+        f[5 * kSearchBlock] = (u32)(M >> 32);
+        f[6 * kSearchBlock] = (u32)alpha;
+        f[7 * kSearchBlock] = (u32)beta;
+        f[8 * kSearchBlock] = w;
+    }
+    __device__ __forceinline__ void load(int depth, u64& P, u64& O, u64& M, int& alpha, int& beta, u32& w) const {
+        const u32* f = at(depth);
+        P = (u64)f[0 * kSearchBlock] | ((u64)f[1 * kSearchBlock] << 32);
+        O = (u64)f[2 * kSearchBlock] | ((u64)f[3 * kSearchBlock] << 32);
+        M = (u64)f[4 * kSearchBlock] | ((u64)f[5 * kSearchBlock] << 32);
+        alpha = (int)f[6 * kSearchBlock];
+        beta = (int)f[7 * kSearchBlock];
+        w = f[8 * kSearchBlock];
+    }
+};
+
+struct SearchArgs {
+    const u64* boards;
+    const uint8_t* turn;
+    int32_t* value;
+    uint8_t* best_move;
+    uint8_t* status;
+    u32* nodes;
+    unsigned long long* work;
+    u64 n;
+    u64 total;  // n + lanes of the grid: what the launch's requests add up to
+    u32 limit;
+    int depth;
+    int8_t w[OTH_EVAL_WEIGHTS];
+};
+
+__device__ __forceinline__ void emit(const SearchArgs& a, u64 i, int value, u32 mv, u32 status, u32 nodes) {
+    if (a.value) a.value[i] = value;
+    if (a.best_move) a.best_move[i] = (uint8_t)mv;
+    if (a.status) a.status[i] = (uint8_t)status;
+    if (a.nodes) a.nodes[i] = nodes;
+}
+
+__global__ __launch_bounds__(kSearchBlock) void search_kernel(SearchArgs a) {
+    __shared__ u32 frames[othm::kFrames * othm::kFields * kSearchBlock];
+    __shared__ int table[othm::kEvalTable];
+    const u32 lane = threadIdx.x;
+    if (lane < (u32)othm::kEvalTable) othm::widen_weight(a.w, (int)lane, table);
+    __syncthreads();
+    LdsStack stk{frames + lane};
+    othm::Lane L;
+    L.depth = -1;
+    u64 idx = 0;
+    bool exhausted = false;  // the lane has made its failing request
+    for (;;) {
+        const bool idle = L.depth < 0;
+        const bool want = idle && !exhausted;
+        const u64 wantm = __ballot(want);
+        const u64 busym = __ballot(!idle);
+        if ((wantm | busym) == 0) break;
+        const u64 cnt = (u64)__popcll(wantm);
+        if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
+            u64 base = 0;
+            if (lane == 0) {
+                base = atomicAdd(a.work, cnt);
+                if (base + cnt == a.total) atomicExch(a.work, 0ull);  // every request is made: reset
+            }
+            base = __shfl(base, 0);
+            if (want) {
+                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
+                if (g >= a.n) {
+                    exhausted = true;
+                } else {
+                    const ulonglong2 b = reinterpret_cast<const ulonglong2*>(a.boards)[g];
+                    const bool white = a.turn && a.turn[g] == OTH_WHITE;
+                    if (b.x & b.y) {
+                        emit(a, g, 0, othm::kNoMove, othm::kInvalid, 0u);
+                    } else {
+                        othm::start(L, white ? b.y : b.x, white ? b.x : b.y, a.depth);
+                        idx = g;
+                    }
+                }
+            }
+        }
+        if (L.depth >= 0) {
+            othm::advance<DeviceRules>(L, stk, table, a.limit);
+            if (L.depth < 0) emit(a, idx, L.value, L.best_mv, L.status, L.nodes);
+        }
+    }
+}
+
+inline int status_of(hipError_t e) { return e == hipSuccess ? OTH_OK : -(int)e; }
+
+int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v && *v ? atoi(v) : dflt;
+}
+
+// blocks of the search kernel a device holds at once, resolved on first use
+constexpr int kMaxDevices = 64;
+std::atomic<int> g_resident[kMaxDevices];
+
+int resident_blocks() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= kMaxDevices) return -1;
+    int r = g_resident[dev].load(std::memory_order_acquire);
+    if (r > 0) return r;
+    int cus = 256, per_cu = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(search_kernel),
+                                                       kSearchBlock, 0);
+    (void)hipGetLastError();
+    r = std::max(cus, 1) * (per_cu > 0 ? per_cu : 4);
+    g_resident[dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
+    return r;
+}
+
+int search_grid(int64_t n) {
+    const int resident = resident_blocks();
+    if (resident <= 0) return -1;
+    const int cap = std::min(std::max(env_int("OTH_SEARCH_BLOCKS", resident), 1), resident);
+    return (int)std::min<int64_t>((n + kSearchBlock - 1) / kSearchBlock, (int64_t)cap);
+}
+
+}  // namespace
+
+extern "C" {
+
+int othm_search(const uint64_t* boards, const uint8_t* turn, int depth, const int8_t* weights, uint32_t node_limit,
+                int32_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes, uint64_t* work, int64_t n,
+                void* stream) {
+    if (n < 0 || !work || !weights || depth < 1 || depth > OTHM_MAX_DEPTH || (n > 0 && !boards)) return OTH_EINVAL;
+    if (n == 0) return OTH_OK;
+    const int grid = search_grid(n);
+    if (grid <= 0) return status_of(hipErrorInvalidDevice);
+    SearchArgs a;
+    a.boards = boards;
+    a.turn = turn;
+    a.value = value;
+    a.best_move = best_move;
+    a.status = status;
+    a.nodes = nodes;
+    a.work = reinterpret_cast<unsigned long long*>(work);
+    a.n = (u64)n;
+    a.total = (u64)n + (u64)grid * kSearchBlock;
+    a.limit = node_limit ? node_limit : OTHM_DEFAULT_NODE_LIMIT;
+    a.depth = depth;
+    for (int k = 0; k < OTH_EVAL_WEIGHTS; k++) a.w[k] = weights[k];
+    search_kernel<<<(unsigned)grid, kSearchBlock, 0, (hipStream_t)stream>>>(a);
+    return status_of(hipGetLastError());
+}
+
+int othm_search_grid(int64_t n) {
+    if (n < 0) return OTH_EINVAL;
+    if (n == 0) return 0;
+    const int grid = search_grid(n);
+    return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
+}
+
+}  // extern "C"

@@ -32,6 +32,10 @@ policy).  ``--params FILE`` loads the table from the file paramgen.py writes
 this one stands in for do: with at most K empty squares and a legal move, the
 move is the exact solver's (ops.solve: best final disc difference, ties to the
 lowest square), whatever the policy.
+``--policy search --depth D`` (D = 1..8) looks D plies ahead: the move is
+ops.search's, a fixed-depth alpha-beta with the eval table at the horizon (one
+launch per ``go``; depth 1 is the "eval" policy's move).  ``--solve-empties``
+still takes precedence where it applies.
 """
 import argparse
 import random
@@ -46,10 +50,13 @@ from .codec import handstr_from_coord
 
 
 class Engine:
-    def __init__(self, name="GPU", policy="greedy", seed=0, weights=None, solve_empties=0):
+    def __init__(self, name="GPU", policy="greedy", seed=0, weights=None, solve_empties=0, depth=1):
         if not 0 <= solve_empties <= _lib.SOLVE_MAX_EMPTIES:
             raise ValueError(f"solve_empties must lie in 0..{_lib.SOLVE_MAX_EMPTIES}")
+        if not 1 <= depth <= _lib.SEARCH_MAX_DEPTH:
+            raise ValueError(f"depth must lie in 1..{_lib.SEARCH_MAX_DEPTH}")
         self.solve_empties = solve_empties
+        self.depth = depth
         self.name = name
         self.policy = policy
         self.rng = random.Random(seed)
@@ -102,6 +109,20 @@ class Engine:
             return None
         return handstr_from_coord(sq & 7, sq >> 3)
 
+    def _choose_searched(self):
+        """The depth-limited search's move for the side to move (one
+        othm_search launch), or None when it gives none (node limit)."""
+        b = self.board
+        bl, wh = b.bitboards()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        boards = ops.from_numpy_u64(np.array([[bl, wh]], np.uint64), dev)
+        side = torch.full((1,), b.turn, dtype=torch.uint8, device=dev)
+        r = ops.search(boards, side, self.depth, weights=self.weights, node_limit=1 << 24)
+        sq = int(r.best_move.cpu()[0])
+        if int(r.status.cpu()[0]) != _lib.SEARCH_SEARCHED or sq > 63:
+            return None
+        return handstr_from_coord(sq & 7, sq >> 3)
+
     def choose(self):
         b = self.board
         puts = b.puttables(b.turn)
@@ -114,7 +135,11 @@ class Engine:
         if self.policy == "random":
             x, y = puts[self.rng.randrange(len(puts))]
             return handstr_from_coord(x, y)
-        if self.policy == "eval":
+        if self.policy == "search" and b.turn in (gboard.Black, gboard.White):
+            mv = self._choose_searched()
+            if mv is not None:
+                return mv
+        if self.policy in ("eval", "search"):  # (search: its LIMIT fall-back)
             return self._choose_eval(puts)
         return self._choose_greedy(puts)
 
@@ -131,7 +156,9 @@ class Engine:
             out(">%s plays %s%s" % (self.name, color, mv.upper() if mv != "PS" else "PS"))
             out("")
         elif cmd == "verbose p":
-            extra = " weights=%s" % self.weights.reshape(-1).tolist() if self.policy == "eval" else ""
+            extra = " weights=%s" % self.weights.reshape(-1).tolist() if self.policy in ("eval", "search") else ""
+            if self.policy == "search":
+                extra = " depth=%d" % self.depth + extra
             if self.solve_empties > 0:
                 extra += " solve_empties=%d" % self.solve_empties
             out("%s policy=%s%s" % (self.name, self.policy, extra))
@@ -166,14 +193,15 @@ class Engine:
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     p.add_argument("--name", default="GPU")
-    p.add_argument("--policy", choices=["random", "greedy", "eval"], default="greedy")
+    p.add_argument("--policy", choices=["random", "greedy", "eval", "search"], default="greedy")
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--params", default=None, help="eval table in the paramgen.py file format (policy eval)")
+    p.add_argument("--params", default=None, help="eval table in the paramgen.py file format (policies eval and search)")
+    p.add_argument("--depth", type=int, default=1, metavar="D", help="plies policy search looks ahead (1..8)")
     p.add_argument("--solve-empties", type=int, default=0, metavar="K",
                    help="play the exact solver's move once at most K squares are empty (0 = never, max 12)")
     a = p.parse_args(argv)
     weights = params.read_paramgen(a.params)[1] if a.params else None
-    eng = Engine(a.name, a.policy, a.seed, weights, a.solve_empties)
+    eng = Engine(a.name, a.policy, a.seed, weights, a.solve_empties, a.depth)
 
     def out(s):
         sys.stdout.write(s + "\n")

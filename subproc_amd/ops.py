@@ -15,6 +15,7 @@ Reference mapping (board.py line numbers):
   hands   -> Board.hands_for_direc     124-139 (any origin, all 8 directions)
   rollout -> GameRunner.play_a_game loop   game_runner.py:165-201
   evaluate -> linear eval of the learner's counts() features
+  search  -> fixed-depth alpha-beta over that eval (what the Edax-protocol engines do)
 """
 import ctypes
 from collections import namedtuple
@@ -457,6 +458,59 @@ def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=Non
     return SolveResult(val, mv, st, nd)
 
 
+SearchResult = namedtuple("SearchResult", "value best_move status nodes")
+
+
+def search(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, work=None):
+    """Depth-limited alpha-beta search (othm_search, include/othello_search.h):
+    every position is searched ``depth`` (1..8) plies deep for its mover (White
+    if turn == 2, else Black) with the linear eval of ``weights`` (int8 [4, 9],
+    default params.DEFAULT_WEIGHTS) at the horizon, scored from the root mover's
+    side; a game decided inside the horizon is worth 2**17 times its disc
+    difference.  Depth 1 chooses the move of the 1-ply "eval" policy; a depth of
+    at least the number of empties gives 2**17 times :func:`solve`'s value.
+
+    Returns SearchResult(value int32, best_move uint8, status uint8, nodes):
+    best_move is the lowest square among the best moves, 64 for a forced pass,
+    255 when the game is over; status is _lib.SEARCH_SEARCHED, SEARCH_INVALID
+    (black & white overlap) or SEARCH_LIMIT (this position's search would have
+    passed ``node_limit`` moves and passes; 0 = the library's default, 2**28).
+    ``nodes`` (uint32 as int32 bits, with ``want_nodes``) is each position's
+    count, else None.
+
+    ``work`` as in :func:`rollout`: default the current stream's
+    :func:`work_word` (shared with the rollouts and solves), required under
+    graph capture.
+    """
+    n = _n(boards)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if work is None and capturing:
+        raise RuntimeError("ops.search under graph capture needs an explicit work word: an int64 (1,) device "
+                           "tensor zeroed before the capture, one per captured launch")
+    if not 0 <= int(node_limit) < 2**32:
+        raise ValueError("node_limit must fit 32 bits")
+    d = boards.device
+    pb = _dev(boards, "boards", torch.int64)
+    pt = _dev(turn, "turn", torch.uint8, (n,), d)
+    val = torch.empty(n, dtype=torch.int32, device=d)
+    mv = torch.empty(n, dtype=torch.uint8, device=d)
+    st = torch.empty(n, dtype=torch.uint8, device=d)
+    nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
+    w = work_word(d) if work is None else work
+    pw = _dev(w, "work", torch.int64, (1,), d)
+    with torch.cuda.device(d):
+        rc = _lib.load().othm_search(pb, pt, int(depth), _weights_ptr(weights), int(node_limit), val.data_ptr(),
+                                     mv.data_ptr(), st.data_ptr(), None if nd is None else nd.data_ptr(), pw, n,
+                                     _stream())
+        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
+            if work is None:
+                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
+            elif not capturing:
+                w.zero_()
+        check(rc, "othm_search")
+    return SearchResult(val, mv, st, nd)
+
+
 def sample_midgame(n, seed, index0=0, device="cuda"):
     """Synthetic reachable mid-game positions + one random legal move each (config 2 inputs)."""
     d = _device(device)
@@ -597,6 +651,7 @@ def from_numpy_u64(a, device="cuda"):
     return torch.from_numpy(a.view(np.int64).copy()).to(device)
 
 
-__all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", "solve", "sample_midgame", "replay",
+__all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", "solve", "search", "sample_midgame",
+           "replay",
            "book_text", "features", "evaluate", "to_numpy_u64", "from_numpy_u64",
            "StepResult", "Result", "RolloutResult", "Positions", "Replay", "BLACK", "WHITE", "PASS", "HIST_BINS"]
