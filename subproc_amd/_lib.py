@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libsubproc_amd_hip.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello.h")
 SOLVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve.h")
 SEARCH_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_search.h")
+PLAY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_play.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -36,6 +37,8 @@ SEARCH_TERMINAL_SCALE = 1 << 17
 SEARCH_SEARCHED, SEARCH_INVALID, SEARCH_LIMIT = 1, 2, 3
 SEARCH_NO_MOVE = 255
 SEARCH_DEFAULT_NODE_LIMIT = 1 << 28
+PLAY_MAX_RANDOM = 10      # include/othello_play.h
+PLAY_MAX_PLIES = 255
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -92,6 +95,13 @@ SEARCH_SIGNATURES = {
     "othm_search_grid": (_I, [_I64]),
 }
 
+# search self-play, include/othello_play.h (its own prefix likewise)
+PLAY_SIGNATURES = {
+    "othp_play": (_I, [_P, _P, _U64, _U64, _P, _P, _I, _I, _I, _I, _I, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P,
+                       _P, _P, _I64, _P]),
+    "othp_play_grid": (_I, [_I64]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -122,7 +132,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise OthelloLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES, **PLAY_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -1,0 +1,294 @@
+// play.hip — search self-play for gfx950: whole games between two searching
+// players in one launch, one lane per game (include/othello_play.h).
+//
+// A lane's search is search_core.hpp's advance(), unchanged; play_core.hpp's
+// step() is the transition that takes a lane from a finished root to the next
+// one: play the move, record it, settle game over / pass / coin / single move,
+// start the new mover's search.  This file gives the two what search.hip gives
+// the search, in the same shape:
+//   * the rules: bitboard.hpp's moves() and flips_carry();
+//   * the stack: an LDS array indexed [depth][field][lane] in 32-bit words; no
+//     per-thread array, no recursion, no scratch;
+//   * both players' eval tables, passed by value with the launch and widened
+//     into LDS (2 x 48 ints) by the block's one wave; a lane's search reads the
+//     table of its mover;
+//   * the refill: idle lanes take the next GAMES from the caller's work word,
+//     kRefillMin of them at a time by one atomic of lane 0, each lane making
+//     one failing request, the completing add resetting the word: search.hip's
+//     protocol at game granularity.
+// The game's state (boards, ply, LCG state and increment, the two budgets, the
+// colour bits, the game index, the node sum) stays in registers.  Move bytes
+// and the per-game outputs are plain vector stores; the histogram is three
+// global atomics per finished game.
+//
+// Bounds: a lane's loop ends.  Every search is bounded by node_limit (at most
+// that many steps that count a node, a constant number of others per node);
+// every game by its plies (60 placements and the passes between them; step()
+// stops a game at 255 whatever its boards); every lane by the games of the
+// launch and one failing request.
+//
+// Geometry: one wave per block.  7 frames x 36 B x 64 lanes + the tables =
+// 16.1 KB of LDS per block, eight blocks in a CU's 160 KB (two waves per SIMD).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <atomic>
+
+#include "../../include/othello.h"
+#include "../../include/othello_play.h"
+#include "../../include/othello_search.h"
+#include "bitboard.hpp"
+#include "play_core.hpp"
+
+static_assert(OTHM_MAX_DEPTH == othm::kMaxDepth && OTHM_SEARCHED == othm::kSearched &&
+                  OTHM_INVALID == othm::kInvalid && OTHM_LIMIT == othm::kLimit && OTH_PASS == othp::kPassMove,
+              "header and core disagree");
+static_assert(OTHP_MAX_RANDOM == othp::kMaxBudget && OTHP_MAX_PLIES == othp::kMaxPlies &&
+                  OTH_MOVES_STRIDE == othp::kMovesStride && OTH_MOVES_STRIDE % 16 == 0,
+              "header and core disagree");
+static_assert(OTH_EVAL_WEIGHTS == othm::kEvalPhases * othm::kEvalFeatures, "the eval table's shape");
+
+namespace {
+
+using othm::u32;
+using othm::u64;
+
+constexpr int kPlayBlock = 64;  // one wave
+constexpr int kRefillMin = 8;   // idle lanes that make a wave refill (solve.hip's measurement)
+
+struct DeviceRules {
+    static __device__ __forceinline__ u64 moves(u64 P, u64 O) { return oth::moves(P, O); }
+    static __device__ __forceinline__ u64 flips(u32 sq, u64 P, u64 O) { return oth::flips_carry(sq, P, O); }
+    static __device__ __forceinline__ u32 lowest(u64 m) { return (u32)__builtin_ctzll(m); }
+    static __device__ __forceinline__ int count(u64 x) { return __popcll(x); }
+    static __device__ __forceinline__ int mul(int w, int c) { return __mul24(w, c); }
+};
+
+// frames [depth][field][lane]; `base` already points at the lane's column
+struct LdsStack {
+    u32* base;
+    __device__ __forceinline__ u32* at(int depth) const { return base + depth * (othm::kFields * kPlayBlock); }
+    __device__ __forceinline__ void store(int depth, u64 P, u64 O, u64 M, int alpha, int beta, u32 w) {
+        u32* f = at(depth);
+        f[0 * kPlayBlock] = (u32)P;
+        f[1 * kPlayBlock] = (u32)(P >> 32);
+        f[2 * kPlayBlock] = (u32)O;
+        f[3 * kPlayBlock] = (u32)(O >> 32);
+        f[4 * kPlayBlock] = (u32)M;
+        f[5 * kPlayBlock] = (u32)(M >> 32);
+        f[6 * kPlayBlock] = (u32)alpha;
+        f[7 * kPlayBlock] = (u32)beta;
+        f[8 * kPlayBlock] = w;
+    }
+    __device__ __forceinline__ void load(int depth, u64& P, u64& O, u64& M, int& alpha, int& beta, u32& w) const {
+        const u32* f = at(depth);
+        P = (u64)f[0 * kPlayBlock] | ((u64)f[1 * kPlayBlock] << 32);
+        O = (u64)f[2 * kPlayBlock] | ((u64)f[3 * kPlayBlock] << 32);
+        M = (u64)f[4 * kPlayBlock] | ((u64)f[5 * kPlayBlock] << 32);
+        alpha = (int)f[6 * kPlayBlock];
+        beta = (int)f[7 * kPlayBlock];
+        w = f[8 * kPlayBlock];
+    }
+};
+
+struct PlayArgs {
+    const u64* start;
+    const uint8_t* start_turn;
+    uint8_t* a_black;
+    u64* final_boards;
+    int8_t* diff;
+    uint8_t* plies;
+    uint8_t* moves;
+    uint8_t* status;
+    u64* nodes;
+    unsigned long long* hist;
+    unsigned long long* work;
+    u64 n;
+    u64 total;  // n + lanes of the grid: what the launch's requests add up to
+    u64 seed_state;
+    u64 game_id0;
+    othp::Match match;
+    int8_t w[2][OTH_EVAL_WEIGHTS];  // A's table, B's table
+};
+
+// a game's move record: the row starts 255-padded, a move is one byte store
+struct MoveRecord {
+    uint8_t* row;  // NULL: no record
+    __device__ __forceinline__ void pad() const {
+        if (!row) return;
+#pragma unroll
+        for (int q = 0; q < OTH_MOVES_STRIDE / 16; q++) reinterpret_cast<uint4*>(row)[q] = make_uint4(~0u, ~0u, ~0u, ~0u);
+    }
+    __device__ __forceinline__ void move(u32 ply, u32 code) const {
+        if (row && ply < (u32)OTH_MOVES_STRIDE) row[ply] = (uint8_t)code;
+    }
+};
+
+// game g has ended (G.status says how): its outputs, and the histogram's bins
+// if it was played to its end
+__device__ __forceinline__ void emit(const PlayArgs& a, u64 g, const othp::Game& G) {
+    const u64 bl = othp::black_of(G), wh = othp::white_of(G);
+    const int d = G.status == othm::kInvalid ? 0 : __popcll(bl) - __popcll(wh);
+    if (a.a_black) a.a_black[g] = (uint8_t)G.a_black;
+    if (a.final_boards) reinterpret_cast<ulonglong2*>(a.final_boards)[g] = make_ulonglong2(bl, wh);
+    if (a.diff) a.diff[g] = (int8_t)d;
+    if (a.plies) a.plies[g] = (uint8_t)G.ply;
+    if (a.status) a.status[g] = (uint8_t)G.status;
+    if (a.nodes) a.nodes[g] = G.nodes;
+    if (a.hist && G.status == othm::kSearched) {
+        atomicAdd(&a.hist[d + 64], 1ull);
+        atomicAdd(&a.hist[d > 0 ? 129 : (d < 0 ? 130 : 131)], 1ull);
+        atomicAdd(&a.hist[132], (unsigned long long)G.ply);
+    }
+}
+
+__global__ __launch_bounds__(kPlayBlock) void play_kernel(PlayArgs a) {
+    __shared__ u32 frames[othm::kFrames * othm::kFields * kPlayBlock];
+    __shared__ int tables[2 * othm::kEvalTable];
+    const u32 lane = threadIdx.x;
+    if (lane < (u32)othm::kEvalTable) {
+        othm::widen_weight(a.w[0], (int)lane, tables);
+        othm::widen_weight(a.w[1], (int)lane, tables + othm::kEvalTable);
+    }
+    __syncthreads();
+    LdsStack stk{frames + lane};
+    othm::Lane L;
+    L.depth = -1;
+    othp::Game G;
+    G.live = false;
+    MoveRecord rec{nullptr};
+    u64 idx = 0;
+    bool exhausted = false;  // the lane has made its failing request
+    for (;;) {
+        const bool idle = !G.live;
+        const bool want = idle && !exhausted;
+        const u64 wantm = __ballot(want);
+        const u64 busym = __ballot(!idle);
+        if ((wantm | busym) == 0) break;
+        const u64 cnt = (u64)__popcll(wantm);
+        if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
+            u64 base = 0;
+            if (lane == 0) {
+                base = atomicAdd(a.work, cnt);
+                if (base + cnt == a.total) atomicExch(a.work, 0ull);  // every request is made: reset
+            }
+            base = __shfl(base, 0);
+            if (want) {
+                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
+                if (g >= a.n) {
+                    exhausted = true;
+                } else {
+                    u64 black = othp::kOpenBlack, white = othp::kOpenWhite;
+                    bool white_to_move = false;
+                    if (a.start) {
+                        const ulonglong2 b = reinterpret_cast<const ulonglong2*>(a.start)[g];
+                        black = b.x;
+                        white = b.y;
+                        white_to_move = a.start_turn && a.start_turn[g] == OTH_WHITE;
+                    }
+                    rec.row = a.moves ? a.moves + g * OTH_MOVES_STRIDE : nullptr;
+                    rec.pad();
+                    othp::begin(G, L, a.match, othp::game_key(a.seed_state, a.game_id0 + g), black, white,
+                                white_to_move);
+                    idx = g;
+                    if (!G.live) emit(a, g, G);  // overlapping boards
+                }
+            }
+        }
+        if (G.live) {
+            othp::advance<DeviceRules>(G, L, stk, tables, a.match, rec);
+            if (!G.live) emit(a, idx, G);
+        }
+    }
+}
+
+inline int status_of(hipError_t e) { return e == hipSuccess ? OTH_OK : -(int)e; }
+
+int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v && *v ? atoi(v) : dflt;
+}
+
+// blocks of the play kernel a device holds at once, resolved on first use
+constexpr int kMaxDevices = 64;
+std::atomic<int> g_resident[kMaxDevices];
+
+int resident_blocks() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= kMaxDevices) return -1;
+    int r = g_resident[dev].load(std::memory_order_acquire);
+    if (r > 0) return r;
+    int cus = 256, per_cu = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(play_kernel), kPlayBlock,
+                                                       0);
+    (void)hipGetLastError();
+    r = std::max(cus, 1) * (per_cu > 0 ? per_cu : 4);
+    g_resident[dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
+    return r;
+}
+
+int play_grid(int64_t n) {
+    const int resident = resident_blocks();
+    if (resident <= 0) return -1;
+    const int cap = std::min(std::max(env_int("OTH_PLAY_BLOCKS", resident), 1), resident);
+    return (int)std::min<int64_t>((n + kPlayBlock - 1) / kPlayBlock, (int64_t)cap);
+}
+
+}  // namespace
+
+extern "C" {
+
+int othp_play(const uint64_t* start, const uint8_t* start_turn, uint64_t seed, uint64_t game_id0,
+              const int8_t* weights_a, const int8_t* weights_b, int depth_a, int depth_b, int exact_empties,
+              int n_rand_a, int n_rand_b, int swap_colours, uint32_t node_limit, uint8_t* a_black,
+              uint64_t* final_boards, int8_t* diff, uint8_t* plies, uint8_t* moves, uint8_t* status, uint64_t* nodes,
+              int64_t* hist, uint64_t* work, int64_t n, void* stream) {
+    if (n < 0 || !work || !weights_a || !weights_b || depth_a < 1 || depth_a > OTHM_MAX_DEPTH || depth_b < 1 ||
+        depth_b > OTHM_MAX_DEPTH || exact_empties < 0 || exact_empties > OTHM_MAX_DEPTH || n_rand_a < 0 || n_rand_b < 0)
+        return OTH_EINVAL;
+    if (n == 0) return OTH_OK;
+    const int grid = play_grid(n);
+    if (grid <= 0) return status_of(hipErrorInvalidDevice);
+    PlayArgs a;
+    a.start = start;
+    a.start_turn = start_turn;
+    a.a_black = a_black;
+    a.final_boards = final_boards;
+    a.diff = diff;
+    a.plies = plies;
+    a.moves = moves;
+    a.status = status;
+    a.nodes = nodes;
+    a.hist = reinterpret_cast<unsigned long long*>(hist);
+    a.work = reinterpret_cast<unsigned long long*>(work);
+    a.n = (u64)n;
+    a.total = (u64)n + (u64)grid * kPlayBlock;
+    a.seed_state = othp::seed_state(seed);
+    a.game_id0 = game_id0;
+    a.match.depth[0] = depth_a;
+    a.match.depth[1] = depth_b;
+    a.match.n_rand[0] = (u32)std::min(n_rand_a, OTHP_MAX_RANDOM);
+    a.match.n_rand[1] = (u32)std::min(n_rand_b, OTHP_MAX_RANDOM);
+    a.match.exact_empties = exact_empties;
+    a.match.limit = node_limit ? node_limit : OTHM_DEFAULT_NODE_LIMIT;
+    a.match.swap = swap_colours != 0;
+    for (int k = 0; k < OTH_EVAL_WEIGHTS; k++) {
+        a.w[0][k] = weights_a[k];
+        a.w[1][k] = weights_b[k];
+    }
+    play_kernel<<<(unsigned)grid, kPlayBlock, 0, (hipStream_t)stream>>>(a);
+    return status_of(hipGetLastError());
+}
+
+int othp_play_grid(int64_t n) {
+    if (n < 0) return OTH_EINVAL;
+    if (n == 0) return 0;
+    const int grid = play_grid(n);
+    return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
+}
+
+}  // extern "C"

@@ -16,6 +16,7 @@ Reference mapping (board.py line numbers):
   rollout -> GameRunner.play_a_game loop   game_runner.py:165-201
   evaluate -> linear eval of the learner's counts() features
   search  -> fixed-depth alpha-beta over that eval (what the Edax-protocol engines do)
+  play    -> GameRunner matches between two such engines, whole games in one launch
 """
 import ctypes
 from collections import namedtuple
@@ -511,6 +512,74 @@ def search(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, wo
     return SearchResult(val, mv, st, nd)
 
 
+PlayResult = namedtuple("PlayResult", "final_boards diff plies moves hist a_black status nodes")
+
+
+def play(n, seed, game_id0=0, weights_a=None, weights_b=None, depth_a=1, depth_b=None, exact_empties=0, n_rand_a=0,
+         n_rand_b=0, swap_colours=False, start=None, start_turn=None, record_moves=False, node_limit=0,
+         want_nodes=False, hist=None, device="cuda", work=None):
+    """n whole games between two searching players in one launch (othp_play,
+    include/othello_play.h): :func:`rollout_runner`'s match schedule -- player
+    A against player B, the colour draw, the random-move budgets -- with every
+    policy move chosen by :func:`search` at the mover's depth (``depth_a``,
+    ``depth_b``, default ``depth_a``; 1..8) over the mover's table
+    (``weights_a`` / ``weights_b``, default params.DEFAULT_WEIGHTS).  A mover
+    without a move passes, a single legal move is played without a search, and
+    once a position has at most ``exact_empties`` (0..8) empty squares the
+    search runs to the end of the game, so the move is :func:`solve`'s.  Game i
+    is global id game_id0 + i.
+
+    Returns PlayResult(final_boards, diff, plies, moves, hist, a_black, status,
+    nodes): the first six as :class:`RunnerResult` (so GameBooks.from_rollout
+    takes it as it is); status is _lib.SEARCH_SEARCHED (played to its end),
+    SEARCH_INVALID (the start boards overlap: nothing played) or SEARCH_LIMIT
+    (a search would have passed ``node_limit`` nodes, 0 = the search's default:
+    the game stops there); ``hist`` counts the finished games only.  ``nodes``
+    (int64, with ``want_nodes``) is the sum of each game's search nodes.
+
+    One lane plays one game: a launch lasts as long as its longest game.
+    ``work`` as in :func:`rollout`."""
+    capturing = torch.cuda.is_current_stream_capturing()
+    if work is None and capturing:
+        raise RuntimeError("ops.play under graph capture needs an explicit work word: an int64 (1,) device "
+                           "tensor zeroed before the capture, one per captured launch")
+    if not 0 <= int(node_limit) < 2**32:
+        raise ValueError("node_limit must fit 32 bits")
+    d = _device(device) if start is None else start.device
+    ps = pst = None
+    if start is not None:
+        if _n(start) != n:
+            raise ValueError("start must have n rows")
+        ps = _dev(start, "start", torch.int64)
+        pst = _opt(start_turn, "start_turn", torch.uint8, (n,), start.device)
+    fb = torch.empty((n, 2), dtype=torch.int64, device=d)
+    df = torch.empty(n, dtype=torch.int8, device=d)
+    pl = torch.empty(n, dtype=torch.uint8, device=d)
+    ab = torch.empty(n, dtype=torch.uint8, device=d)
+    st = torch.empty(n, dtype=torch.uint8, device=d)
+    mv = torch.empty((n, MOVES_STRIDE), dtype=torch.uint8, device=d) if record_moves else None
+    nd = torch.empty(n, dtype=torch.int64, device=d) if want_nodes else None
+    if hist is None:
+        hist = torch.zeros(HIST_BINS, dtype=torch.int64, device=d)
+    ph = _dev(hist, "hist", torch.int64, (HIST_BINS,), d)
+    w = work_word(d) if work is None else work
+    pw = _dev(w, "work", torch.int64, (1,), d)
+    with torch.cuda.device(d):
+        rc = _lib.load().othp_play(ps, pst, seed & (2**64 - 1), game_id0, _weights_ptr(weights_a),
+                                   _weights_ptr(weights_b), int(depth_a), int(depth_a if depth_b is None else depth_b),
+                                   int(exact_empties), int(n_rand_a), int(n_rand_b), int(bool(swap_colours)),
+                                   int(node_limit), ab.data_ptr(), fb.data_ptr(), df.data_ptr(), pl.data_ptr(),
+                                   None if mv is None else mv.data_ptr(), st.data_ptr(),
+                                   None if nd is None else nd.data_ptr(), ph, pw, n, _stream())
+        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
+            if work is None:
+                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
+            elif not capturing:
+                w.zero_()
+        check(rc, "othp_play")
+    return PlayResult(fb, df, pl, mv, hist, ab, st, nd)
+
+
 def sample_midgame(n, seed, index0=0, device="cuda"):
     """Synthetic reachable mid-game positions + one random legal move each (config 2 inputs)."""
     d = _device(device)
@@ -651,7 +720,7 @@ def from_numpy_u64(a, device="cuda"):
     return torch.from_numpy(a.view(np.int64).copy()).to(device)
 
 
-__all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", "solve", "search", "sample_midgame",
+__all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", "solve", "search", "play", "sample_midgame",
            "replay",
            "book_text", "features", "evaluate", "to_numpy_u64", "from_numpy_u64",
-           "StepResult", "Result", "RolloutResult", "Positions", "Replay", "BLACK", "WHITE", "PASS", "HIST_BINS"]
+           "StepResult", "Result", "RolloutResult", "PlayResult", "Positions", "Replay", "BLACK", "WHITE", "PASS", "HIST_BINS"]

@@ -18,7 +18,9 @@ returns (194-199), and the batch statistics LearnBasePlus.store_batch_stats
 derives from the books (learn_base.py:58-110).
 
 The schedule runs inside the rollout kernel (oth_rollout_runner,
-include/othello.h); its draws come from each game's counter RNG stream
+include/othello.h) for the 1-ply policies and inside the self-play kernel
+(othp_play, include/othello_play.h) for policy "search", where both players
+look ahead; its draws come from each game's counter RNG stream
 (DESIGN.md §4), so a batch is reproducible from (seed, game ids) and any
 split of the ids over launches or GPUs plays the same games.
 """
@@ -34,17 +36,28 @@ MatchBatch = namedtuple("MatchBatch", "games books meta won stats a_black")
 N_RAND_HAND_UNTIL = 10  # game_runner.py:6
 
 
-def hamlet_param_line(name, policy, weights):
+def hamlet_param_line(name, policy, weights, depth=None, solve_empties=0):
     """The 'verbose p' line of the GPU engine (subproc_amd.engine): what
-    GameRunner.extract_hamlet_param stores as 'hamletparam' (game_runner.py:124-130)."""
-    extra = " weights=%s" % params.as_weights(weights).reshape(-1).tolist() if policy == "eval" else ""
+    GameRunner.extract_hamlet_param stores as 'hamletparam' (game_runner.py:124-130).
+    For policy "search": the engine's depth before the weights and, if set,
+    its solve_empties after them."""
+    extra = " weights=%s" % params.as_weights(weights).reshape(-1).tolist() if policy in ("eval", "search") else ""
+    if policy == "search":
+        extra = " depth=%d" % depth + extra
+        if solve_empties > 0:
+            extra += " solve_empties=%d" % solve_empties
     return "%s policy=%s%s" % (name, policy, extra)
 
 
 def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, policy="eval", name_a="Hamlet",
-               name_b="GPU", device="cuda", record=True, win_rule="reference", store=None):
+               name_b="GPU", device="cuda", record=True, win_rule="reference", store=None, depth=None,
+               exact_empties=0):
     """n GameRunner games between A (``weights_a``) and B (``weights_b``,
-    default params.DEFAULT_WEIGHTS), both playing ``policy``.
+    default params.DEFAULT_WEIGHTS), both playing ``policy``: "greedy", "eval",
+    or "search" -- every policy move searched ``depth`` plies deep (an int, or
+    (A's, B's); 1..8) over the mover's table, exactly from ``exact_empties``
+    empty squares on (ops.play: the whole games in one launch).  A "search"
+    game that a search's node limit stopped (ops.play's status) raises.
 
     Game i is global id ``game_id0 + i`` (its book id).  ``record=True``
     replays every game into books (the recorder's view); the batch stats are
@@ -57,12 +70,25 @@ def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, po
     swap = int(conf.get("proc_randomize_black_white", 0)) == 1
     wa = params.DEFAULT_WEIGHTS if weights_a is None else weights_a
     wb = params.DEFAULT_WEIGHTS if weights_b is None else weights_b
-    r = ops.rollout_runner(n, seed, game_id0, policy, wa, wb, n_rand_a, n_rand_b, swap, record_moves=record,
-                           device=device)
+    if policy == "search":
+        if depth is None:
+            raise ValueError("policy 'search' needs depth=D or depth=(Da, Db)")
+        depth_a, depth_b = (depth, depth) if isinstance(depth, int) else depth
+        r = ops.play(n, seed, game_id0, wa, wb, depth_a, depth_b, exact_empties, n_rand_a, n_rand_b, swap,
+                     record_moves=record, device=device)
+        if not bool((r.status == ops._lib.SEARCH_SEARCHED).all()):
+            raise RuntimeError("do_matches: a game's search reached the node limit")
+        line = {"a": hamlet_param_line(name_a, policy, wa, depth_a, exact_empties),
+                "b": hamlet_param_line(name_b, policy, wb, depth_b, exact_empties)}
+    else:
+        if depth is not None or exact_empties:
+            raise ValueError("depth and exact_empties apply to policy 'search' only")
+        r = ops.rollout_runner(n, seed, game_id0, policy, wa, wb, n_rand_a, n_rand_b, swap, record_moves=record,
+                               device=device)
+        line = {"a": hamlet_param_line(name_a, policy, wa), "b": hamlet_param_line(name_b, policy, wb)}
     a_black = r.a_black.cpu().numpy().astype(bool)
     # extract_hamlet_param (game_runner.py:124-130): Black's engine first, then
     # White's, per game (the colours follow the swap draw)
-    line = {"a": hamlet_param_line(name_a, policy, wa), "b": hamlet_param_line(name_b, policy, wb)}
 
     def hamlet(black, white):
         for who, name in (black, white):

@@ -1,0 +1,176 @@
+// play_host.cpp — the search self-play's game driver
+// (subproc_amd/csrc/play_core.hpp around search_core.hpp) on the host, with a
+// plain C++ statement of the rules and OpenMP over games.
+//
+// Two uses, as search_host.cpp's:
+//   * the driver's logic can be run under -fsanitize=address,undefined and
+//     compared against tests/play_ref.py's games before any GPU run (the device
+//     build differs in the rules struct, the stack and the outputs' stores);
+//   * the CPU context line of tools/play_bench.py (16 threads).
+//
+// build:  g++ -O2 -std=c++17 -fopenmp -o tools/diag/play_host tools/diag/play_host.cpp
+// run:    play_host ARGS OUT [threads=16]
+//   ARGS: a text file,
+//           line 1: n seed game_id0 depth_a depth_b exact_empties n_rand_a n_rand_b swap node_limit have_start
+//           line 2: A's 36 weights, line 3: B's 36 weights (integers -128..127)
+//           then, with have_start != 0, n lines "<black hex> <white hex> <turn>"
+//   OUT:  one line per game,
+//           "<a_black> <black hex> <white hex> <diff> <plies> <status> <nodes> <128 move bytes as hex>"
+//   stderr: one JSON line with the wall time
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../subproc_amd/csrc/play_core.hpp"
+
+using othm::u32;
+using othm::u64;
+
+struct HostRules {
+    static constexpr int dx[8] = {1, -1, 0, 0, 1, -1, -1, 1};
+    static constexpr int dy[8] = {0, 0, 1, -1, 1, -1, 1, -1};
+    static int count(u64 x) { return __builtin_popcountll(x); }
+    static u32 lowest(u64 m) { return (u32)__builtin_ctzll(m); }
+    static int mul(int w, int c) { return w * c; }
+    // the opponent discs the move on empty square sq turns over
+    static u64 flips(u32 sq, u64 P, u64 O) {
+        u64 all = 0;
+        for (int d = 0; d < 8; d++) {
+            int x = (int)(sq & 7) + dx[d], y = (int)(sq >> 3) + dy[d];
+            u64 run = 0;
+            while (x >= 0 && x < 8 && y >= 0 && y < 8 && (O >> (x + 8 * y) & 1)) {
+                run |= 1ull << (x + 8 * y);
+                x += dx[d];
+                y += dy[d];
+            }
+            if (run && x >= 0 && x < 8 && y >= 0 && y < 8 && (P >> (x + 8 * y) & 1)) all |= run;
+        }
+        return all;
+    }
+    static u64 moves(u64 P, u64 O) {
+        u64 m = 0;
+        for (u64 e = ~(P | O); e; e &= e - 1) {
+            const u32 sq = lowest(e);
+            if (flips(sq, P, O)) m |= 1ull << sq;
+        }
+        return m;
+    }
+};
+
+struct HostStack {
+    u64 P[othm::kFrames], O[othm::kFrames], M[othm::kFrames];
+    int a[othm::kFrames], b[othm::kFrames];
+    u32 w[othm::kFrames];
+    void store(int d, u64 p, u64 o, u64 m, int al, int be, u32 ww) {
+        P[d] = p, O[d] = o, M[d] = m, a[d] = al, b[d] = be, w[d] = ww;
+    }
+    void load(int d, u64& p, u64& o, u64& m, int& al, int& be, u32& ww) const {
+        p = P[d], o = O[d], m = M[d], al = a[d], be = b[d], ww = w[d];
+    }
+};
+
+struct Start {
+    u64 black, white;
+    int turn;
+};
+struct Out {
+    int a_black, diff;
+    u64 black, white, nodes;
+    u32 plies, status;
+    uint8_t moves[othp::kMovesStride];
+    void move(u32 ply, u32 code) {
+        if (ply < othp::kMovesStride) moves[ply] = (uint8_t)code;
+    }
+};
+
+static void play_one(const Start& s, u64 key, const othp::Match& m, const int* tables, Out& out) {
+    memset(out.moves, 255, sizeof out.moves);
+    othp::Game G;
+    othm::Lane L;
+    HostStack stk;
+    othp::begin(G, L, m, key, s.black, s.white, s.turn == 2);
+    while (G.live) othp::advance<HostRules>(G, L, stk, tables, m, out);
+    out.a_black = G.a_black;
+    out.black = othp::black_of(G);
+    out.white = othp::white_of(G);
+    out.diff = G.status == othm::kInvalid ? 0 : HostRules::count(out.black) - HostRules::count(out.white);
+    out.plies = G.ply;
+    out.status = G.status;
+    out.nodes = G.nodes;
+}
+
+static bool read_weights(FILE* f, int8_t* w36) {
+    for (int k = 0; k < othm::kEvalPhases * othm::kEvalFeatures; k++) {
+        int v;
+        if (fscanf(f, "%d", &v) != 1 || v < -128 || v > 127) return false;
+        w36[k] = (int8_t)v;
+    }
+    return true;
+}
+
+int main(int argc, char** argv) {
+    if (argc < 3) {
+        fprintf(stderr, "usage: %s ARGS OUT [threads]\n", argv[0]);
+        return 2;
+    }
+    const int threads = argc > 3 ? atoi(argv[3]) : 16;
+    if (threads < 1) return 2;
+    FILE* in = fopen(argv[1], "r");
+    if (!in) return 1;
+    long n;
+    unsigned long long seed, id0, limit_arg;
+    int da, db, exact, ra, rb, swap, have_start;
+    if (fscanf(in, "%ld %llu %llu %d %d %d %d %d %d %llu %d", &n, &seed, &id0, &da, &db, &exact, &ra, &rb, &swap,
+               &limit_arg, &have_start) != 11)
+        return 2;
+    if (n < 0 || da < 1 || da > othm::kMaxDepth || db < 1 || db > othm::kMaxDepth || exact < 0 ||
+        exact > othm::kMaxDepth || ra < 0 || rb < 0 || limit_arg > 0xFFFFFFFFull)
+        return 2;
+    int8_t w36[2][othm::kEvalPhases * othm::kEvalFeatures];
+    if (!read_weights(in, w36[0]) || !read_weights(in, w36[1])) return 2;
+    int tables[2 * othm::kEvalTable];
+    for (int p = 0; p < 2; p++)
+        for (int e = 0; e < othm::kEvalTable; e++) othm::widen_weight(w36[p], e, tables + p * othm::kEvalTable);
+    std::vector<Start> starts((size_t)n, Start{othp::kOpenBlack, othp::kOpenWhite, 1});
+    if (have_start)
+        for (long i = 0; i < n; i++) {
+            unsigned long long b, w;
+            int t;
+            if (fscanf(in, "%llx %llx %d", &b, &w, &t) != 3) return 2;
+            starts[(size_t)i] = Start{b, w, t};
+        }
+    fclose(in);
+    othp::Match m;
+    m.depth[0] = da;
+    m.depth[1] = db;
+    m.n_rand[0] = (u32)(ra < (int)othp::kMaxBudget ? ra : (int)othp::kMaxBudget);
+    m.n_rand[1] = (u32)(rb < (int)othp::kMaxBudget ? rb : (int)othp::kMaxBudget);
+    m.exact_empties = exact;
+    m.limit = limit_arg ? (u32)limit_arg : (1u << 28);
+    m.swap = swap != 0;
+    const u64 S = othp::seed_state(seed);
+    std::vector<Out> out((size_t)n);
+    const auto t0 = std::chrono::steady_clock::now();
+#pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
+    for (long i = 0; i < n; i++) play_one(starts[(size_t)i], othp::game_key(S, id0 + (u64)i), m, tables, out[(size_t)i]);
+    const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    FILE* o = fopen(argv[2], "w");
+    if (!o) return 1;
+    unsigned long long nodes = 0, plies = 0;
+    for (const Out& r : out) {
+        fprintf(o, "%d %llx %llx %d %u %u %llu ", r.a_black, (unsigned long long)r.black, (unsigned long long)r.white,
+                r.diff, r.plies, r.status, (unsigned long long)r.nodes);
+        for (u32 k = 0; k < othp::kMovesStride; k++) fprintf(o, "%02x", r.moves[k]);
+        fprintf(o, "\n");
+        nodes += r.nodes;
+        plies += r.plies;
+    }
+    fclose(o);
+    fprintf(stderr,
+            "{\"games\": %ld, \"threads\": %d, \"depth_a\": %d, \"depth_b\": %d, \"seconds\": %.6f, "
+            "\"games_per_s\": %.1f, \"plies\": %llu, \"nodes\": %llu}\n",
+            n, threads, da, db, sec, sec > 0 ? n / sec : 0.0, plies, nodes);
+    return 0;
+}
