@@ -12,6 +12,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello.h")
 SOLVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve.h")
 SEARCH_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_search.h")
 PLAY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_play.h")
+TREE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_tree.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -39,6 +40,10 @@ SEARCH_NO_MOVE = 255
 SEARCH_DEFAULT_NODE_LIMIT = 1 << 28
 PLAY_MAX_RANDOM = 10      # include/othello_play.h
 PLAY_MAX_PLIES = 255
+TREE_MAX_SPLIT = 4        # include/othello_tree.h
+TREE_NOROOM = 4
+TREE_MIN_NODES = 64
+TREE_DEFAULT_NODES = 32768
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -102,6 +107,13 @@ PLAY_SIGNATURES = {
     "othp_play_grid": (_I, [_I64]),
 }
 
+# the split search, include/othello_tree.h (its own prefix likewise)
+TREE_SIGNATURES = {
+    "otht_search": (_I, [_P, _P, _I, _I, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _I64, ctypes.c_int32, _P, _I64, _P]),
+    "otht_scratch_bytes": (_I64, [_I64, ctypes.c_int32]),
+    "otht_search_grid": (_I, [_I64]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -132,7 +144,8 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:
         raise OthelloLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES, **PLAY_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES, **PLAY_SIGNATURES,
+                              **TREE_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

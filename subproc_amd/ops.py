@@ -462,7 +462,8 @@ def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=Non
 SearchResult = namedtuple("SearchResult", "value best_move status nodes")
 
 
-def search(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, work=None):
+def search(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, work=None, split=0,
+           nodes_per_position=_lib.TREE_DEFAULT_NODES):
     """Depth-limited alpha-beta search (othm_search, include/othello_search.h):
     every position is searched ``depth`` (1..8) plies deep for its mover (White
     if turn == 2, else Black) with the linear eval of ``weights`` (int8 [4, 9],
@@ -482,6 +483,17 @@ def search(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, wo
     ``work`` as in :func:`rollout`: default the current stream's
     :func:`work_word` (shared with the rollouts and solves), required under
     graph capture.
+
+    ``split`` >= 1 (up to 4) is the split search (otht_search,
+    include/othello_tree.h): the top ``split`` plies of every position are
+    expanded into a tree of at most ``nodes_per_position`` nodes in device
+    memory and the nodes at its bottom are searched by all the device's lanes,
+    sharing bounds.  Values and moves are the same; ``depth`` may go to
+    8 + split; ``node_limit`` bounds each task; a position whose tree does not
+    fit its slab far enough down ends as _lib.TREE_NOROOM (value 0, move 255);
+    ``nodes`` then depends on timing.  It pays for small batches, down to one
+    position.  The scratch (otht_scratch_bytes) is allocated here, so this
+    form does not run under graph capture.
     """
     n = _n(boards)
     capturing = torch.cuda.is_current_stream_capturing()
@@ -490,6 +502,9 @@ def search(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, wo
                            "tensor zeroed before the capture, one per captured launch")
     if not 0 <= int(node_limit) < 2**32:
         raise ValueError("node_limit must fit 32 bits")
+    if int(split) != 0:
+        return _search_split(boards, turn, n, int(depth), int(split), weights, int(node_limit), want_nodes, work,
+                             int(nodes_per_position), capturing)
     d = boards.device
     pb = _dev(boards, "boards", torch.int64)
     pt = _dev(turn, "turn", torch.uint8, (n,), d)
@@ -509,6 +524,40 @@ def search(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, wo
             elif not capturing:
                 w.zero_()
         check(rc, "othm_search")
+    return SearchResult(val, mv, st, nd)
+
+
+def _search_split(boards, turn, n, depth, split, weights, node_limit, want_nodes, work, nodes_per_position, capturing):
+    """:func:`search` with split >= 1: otht_search on a scratch of its own."""
+    if capturing:
+        raise RuntimeError("ops.search(split >= 1) allocates its scratch and does not run under graph capture")
+    if not -2**31 <= nodes_per_position < 2**31:
+        raise ValueError("nodes_per_position must fit 32 bits")
+    d = boards.device
+    pb = _dev(boards, "boards", torch.int64)
+    pt = _dev(turn, "turn", torch.uint8, (n,), d)
+    lib = _lib.load()
+    size = lib.otht_scratch_bytes(n, nodes_per_position)
+    if size < 0:
+        check(int(size), "otht_scratch_bytes")
+    val = torch.empty(n, dtype=torch.int32, device=d)
+    mv = torch.empty(n, dtype=torch.uint8, device=d)
+    st = torch.empty(n, dtype=torch.uint8, device=d)
+    nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
+    scratch = torch.empty(max(int(size), 8) // 8, dtype=torch.int64, device=d)
+    w = work_word(d) if work is None else work
+    pw = _dev(w, "work", torch.int64, (1,), d)
+    with torch.cuda.device(d):
+        rc = lib.otht_search(pb, pt, depth, split, _weights_ptr(weights), node_limit, val.data_ptr(), mv.data_ptr(),
+                             st.data_ptr(), None if nd is None else nd.data_ptr(), scratch.data_ptr(),
+                             scratch.numel() * 8, nodes_per_position, pw, n, _stream())
+        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
+            if work is None:
+                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
+            else:
+                w.zero_()
+        check(rc, "otht_search")
+    # (the caching allocator hands the scratch to later work of THIS stream only)
     return SearchResult(val, mv, st, nd)
 
 
