@@ -13,6 +13,7 @@ SOLVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve.h"
 SEARCH_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_search.h")
 PLAY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_play.h")
 TREE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_tree.h")
+ORDER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_order.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -44,6 +45,7 @@ TREE_MAX_SPLIT = 4        # include/othello_tree.h
 TREE_NOROOM = 4
 TREE_MIN_NODES = 64
 TREE_DEFAULT_NODES = 32768
+ORDER_MAX = 1             # include/othello_order.h
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -114,6 +116,19 @@ TREE_SIGNATURES = {
     "otht_search_grid": (_I, [_I64]),
 }
 
+# the ordered searches, include/othello_order.h (its own prefix likewise): the
+# three calls above with `order` after depth / split / exact_empties
+ORDER_SIGNATURES = {
+    "otho_search_ordered": (_I, [_P, _P, _I, _I, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _I64, _P]),
+    "otho_play_ordered": (_I, [_P, _P, _U64, _U64, _P, _P, _I, _I, _I, _I, _I, _I, _I, ctypes.c_uint32, _P, _P, _P, _P,
+                               _P, _P, _P, _P, _P, _I64, _P]),
+    "otho_tree_ordered": (_I, [_P, _P, _I, _I, _I, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _I64, ctypes.c_int32, _P,
+                               _I64, _P]),
+    "otho_search_ordered_grid": (_I, [_I64, _I]),
+    "otho_play_ordered_grid": (_I, [_I64, _I]),
+    "otho_tree_ordered_grid": (_I, [_I64, _I]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -145,7 +160,7 @@ def load():
     except OSError as e:
         raise OthelloLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES, **PLAY_SIGNATURES,
-                              **TREE_SIGNATURES}.items():
+                              **TREE_SIGNATURES, **ORDER_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -21,6 +21,10 @@
 // and the per-game outputs are plain vector stores; the histogram is three
 // global atomics per finished game.
 //
+// play_ordered_kernel is the same loop with order_core.hpp's ordered search
+// inside (include/othello_order.h, order = 1; play_core.hpp's
+// advance_ordered()); both kernels are instances of play_body<>.
+//
 // Bounds: a lane's loop ends.  Every search is bounded by node_limit (at most
 // that many steps that count a node, a constant number of others per node);
 // every game by its plies (60 placements and the passes between them; step()
@@ -39,6 +43,7 @@
 #include "../../include/othello.h"
 #include "../../include/othello_play.h"
 #include "../../include/othello_search.h"
+#include "../../include/othello_order.h"
 #include "bitboard.hpp"
 #include "play_core.hpp"
 
@@ -144,7 +149,9 @@ __device__ __forceinline__ void emit(const PlayArgs& a, u64 g, const othp::Game&
     }
 }
 
-__global__ __launch_bounds__(kPlayBlock) void play_kernel(PlayArgs a) {
+// the persistent loop of both kernels; kOrdered: order_core.hpp's machine
+template <bool kOrdered>
+__device__ __forceinline__ void play_body(const PlayArgs& a) {
     __shared__ u32 frames[othm::kFrames * othm::kFields * kPlayBlock];
     __shared__ int tables[2 * othm::kEvalTable];
     const u32 lane = threadIdx.x;
@@ -156,6 +163,8 @@ __global__ __launch_bounds__(kPlayBlock) void play_kernel(PlayArgs a) {
     LdsStack stk{frames + lane};
     othm::Lane L;
     L.depth = -1;
+    othm::Order Q;  // (unused, and gone, when !kOrdered)
+    othm::order_reset(Q);
     othp::Game G;
     G.live = false;
     MoveRecord rec{nullptr};
@@ -198,11 +207,17 @@ __global__ __launch_bounds__(kPlayBlock) void play_kernel(PlayArgs a) {
             }
         }
         if (G.live) {
-            othp::advance<DeviceRules>(G, L, stk, tables, a.match, rec);
+            if constexpr (kOrdered)
+                othp::advance_ordered<DeviceRules>(G, L, Q, stk, tables, a.match, rec);
+            else
+                othp::advance<DeviceRules>(G, L, stk, tables, a.match, rec);
             if (!G.live) emit(a, idx, G);
         }
     }
 }
+
+__global__ __launch_bounds__(kPlayBlock) void play_kernel(PlayArgs a) { play_body<false>(a); }
+__global__ __launch_bounds__(kPlayBlock) void play_ordered_kernel(PlayArgs a) { play_body<true>(a); }
 
 inline int status_of(hipError_t e) { return e == hipSuccess ? OTH_OK : -(int)e; }
 
@@ -211,28 +226,30 @@ int env_int(const char* name, int dflt) {
     return v && *v ? atoi(v) : dflt;
 }
 
-// blocks of the play kernel a device holds at once, resolved on first use
+// blocks of the play kernel (order 0) or the ordered one (1) a device holds at
+// once, resolved on first use
 constexpr int kMaxDevices = 64;
-std::atomic<int> g_resident[kMaxDevices];
+std::atomic<int> g_resident[2][kMaxDevices];
 
-int resident_blocks() {
+int resident_blocks(int order) {
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= kMaxDevices) return -1;
-    int r = g_resident[dev].load(std::memory_order_acquire);
+    int r = g_resident[order][dev].load(std::memory_order_acquire);
     if (r > 0) return r;
     int cus = 256, per_cu = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(play_kernel), kPlayBlock,
-                                                       0);
+    const void* kernel = order ? reinterpret_cast<const void*>(play_ordered_kernel)
+                               : reinterpret_cast<const void*>(play_kernel);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kPlayBlock, 0);
     (void)hipGetLastError();
     r = std::max(cus, 1) * (per_cu > 0 ? per_cu : 4);
-    g_resident[dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
+    g_resident[order][dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
     return r;
 }
 
-int play_grid(int64_t n) {
-    const int resident = resident_blocks();
+int play_grid(int64_t n, int order) {
+    const int resident = resident_blocks(order);
     if (resident <= 0) return -1;
     const int cap = std::min(std::max(env_int("OTH_PLAY_BLOCKS", resident), 1), resident);
     return (int)std::min<int64_t>((n + kPlayBlock - 1) / kPlayBlock, (int64_t)cap);
@@ -242,16 +259,17 @@ int play_grid(int64_t n) {
 
 extern "C" {
 
-int othp_play(const uint64_t* start, const uint8_t* start_turn, uint64_t seed, uint64_t game_id0,
-              const int8_t* weights_a, const int8_t* weights_b, int depth_a, int depth_b, int exact_empties,
-              int n_rand_a, int n_rand_b, int swap_colours, uint32_t node_limit, uint8_t* a_black,
-              uint64_t* final_boards, int8_t* diff, uint8_t* plies, uint8_t* moves, uint8_t* status, uint64_t* nodes,
-              int64_t* hist, uint64_t* work, int64_t n, void* stream) {
+int otho_play_ordered(const uint64_t* start, const uint8_t* start_turn, uint64_t seed, uint64_t game_id0,
+                      const int8_t* weights_a, const int8_t* weights_b, int depth_a, int depth_b, int exact_empties,
+                      int order, int n_rand_a, int n_rand_b, int swap_colours, uint32_t node_limit, uint8_t* a_black,
+                      uint64_t* final_boards, int8_t* diff, uint8_t* plies, uint8_t* moves, uint8_t* status,
+                      uint64_t* nodes, int64_t* hist, uint64_t* work, int64_t n, void* stream) {
+    if (order < 0 || order > OTHO_MAX_ORDER) return OTH_EINVAL;
     if (n < 0 || !work || !weights_a || !weights_b || depth_a < 1 || depth_a > OTHM_MAX_DEPTH || depth_b < 1 ||
         depth_b > OTHM_MAX_DEPTH || exact_empties < 0 || exact_empties > OTHM_MAX_DEPTH || n_rand_a < 0 || n_rand_b < 0)
         return OTH_EINVAL;
     if (n == 0) return OTH_OK;
-    const int grid = play_grid(n);
+    const int grid = play_grid(n, order);
     if (grid <= 0) return status_of(hipErrorInvalidDevice);
     PlayArgs a;
     a.start = start;
@@ -280,15 +298,30 @@ int othp_play(const uint64_t* start, const uint8_t* start_turn, uint64_t seed, u
         a.w[0][k] = weights_a[k];
         a.w[1][k] = weights_b[k];
     }
-    play_kernel<<<(unsigned)grid, kPlayBlock, 0, (hipStream_t)stream>>>(a);
+    if (order)
+        play_ordered_kernel<<<(unsigned)grid, kPlayBlock, 0, (hipStream_t)stream>>>(a);
+    else
+        play_kernel<<<(unsigned)grid, kPlayBlock, 0, (hipStream_t)stream>>>(a);
     return status_of(hipGetLastError());
 }
 
-int othp_play_grid(int64_t n) {
-    if (n < 0) return OTH_EINVAL;
+int othp_play(const uint64_t* start, const uint8_t* start_turn, uint64_t seed, uint64_t game_id0,
+              const int8_t* weights_a, const int8_t* weights_b, int depth_a, int depth_b, int exact_empties,
+              int n_rand_a, int n_rand_b, int swap_colours, uint32_t node_limit, uint8_t* a_black,
+              uint64_t* final_boards, int8_t* diff, uint8_t* plies, uint8_t* moves, uint8_t* status, uint64_t* nodes,
+              int64_t* hist, uint64_t* work, int64_t n, void* stream) {
+    return otho_play_ordered(start, start_turn, seed, game_id0, weights_a, weights_b, depth_a, depth_b, exact_empties, 0,
+                             n_rand_a, n_rand_b, swap_colours, node_limit, a_black, final_boards, diff, plies, moves,
+                             status, nodes, hist, work, n, stream);
+}
+
+int otho_play_ordered_grid(int64_t n, int order) {
+    if (order < 0 || order > OTHO_MAX_ORDER || n < 0) return OTH_EINVAL;
     if (n == 0) return 0;
-    const int grid = play_grid(n);
+    const int grid = play_grid(n, order);
     return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
 }
+
+int othp_play_grid(int64_t n) { return otho_play_ordered_grid(n, 0); }
 
 }  // extern "C"

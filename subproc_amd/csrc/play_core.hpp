@@ -21,6 +21,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "order_core.hpp"
 #include "search_core.hpp"
 
 namespace othp {
@@ -211,6 +212,19 @@ template <class R, class S, class Out>
 OTHM_FN void advance(Game& G, othm::Lane& L, S& stk, const int* tables, const Match& m, Out& out) {
     if (L.depth >= 0) othm::advance<R>(L, stk, tables + othm::kEvalTable * (int)mover_player(G), m.limit);
     if (L.depth < 0) step<R>(G, L, m, out);
+}
+
+// advance() with order_core.hpp's ordered search (both players use it; the games'
+// moves are the same).  Q: the lane's scoring state, reset with every new root.
+template <class R, class S, class Out>
+OTHM_FN void advance_ordered(Game& G, othm::Lane& L, othm::Order& Q, S& stk, const int* tables, const Match& m,
+                             Out& out) {
+    if (L.depth >= 0)
+        othm::advance_ordered<R, true>(L, Q, stk, tables + othm::kEvalTable * (int)mover_player(G), m.limit);
+    if (L.depth < 0) {
+        step<R>(G, L, m, out);
+        othm::order_reset(Q);
+    }
 }
 
 }  // namespace othp

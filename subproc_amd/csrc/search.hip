@@ -15,6 +15,11 @@
 //     solve.hip does (its header has the contract and the measurement behind
 //     the 8).
 //
+// search_ordered_kernel is the same loop around order_core.hpp's
+// advance_ordered() (include/othello_order.h, order = 1): the lane's scoring
+// state is three registers beside its Lane, the frames are the same 9 words.
+// Both kernels are instances of search_body<>; order 0 launches search_kernel.
+//
 // Geometry: one wave per block.  7 frames x 36 B x 64 lanes + the table =
 // 15.9 KB of LDS per block, eight blocks in a CU's 160 KB (two waves per
 // SIMD).  The waves share nothing; the one barrier orders the table's fill.
@@ -27,7 +32,9 @@
 
 #include "../../include/othello.h"
 #include "../../include/othello_search.h"
+#include "../../include/othello_order.h"
 #include "bitboard.hpp"
+#include "order_core.hpp"
 #include "search_core.hpp"
 
 static_assert(OTHM_MAX_DEPTH == othm::kMaxDepth && OTHM_TERMINAL_SCALE == othm::kTerminal, "header and core disagree");
@@ -104,7 +111,9 @@ __device__ __forceinline__ void emit(const SearchArgs& a, u64 i, int value, u32 
     if (a.nodes) a.nodes[i] = nodes;
 }
 
-__global__ __launch_bounds__(kSearchBlock) void search_kernel(SearchArgs a) {
+// the persistent loop of both kernels; kOrdered: order_core.hpp's machine
+template <bool kOrdered>
+__device__ __forceinline__ void search_body(const SearchArgs& a) {
     __shared__ u32 frames[othm::kFrames * othm::kFields * kSearchBlock];
     __shared__ int table[othm::kEvalTable];
     const u32 lane = threadIdx.x;
@@ -113,6 +122,8 @@ __global__ __launch_bounds__(kSearchBlock) void search_kernel(SearchArgs a) {
     LdsStack stk{frames + lane};
     othm::Lane L;
     L.depth = -1;
+    othm::Order Q;  // (unused, and gone, when !kOrdered)
+    othm::order_reset(Q);
     u64 idx = 0;
     bool exhausted = false;  // the lane has made its failing request
     for (;;) {
@@ -140,17 +151,24 @@ __global__ __launch_bounds__(kSearchBlock) void search_kernel(SearchArgs a) {
                         emit(a, g, 0, othm::kNoMove, othm::kInvalid, 0u);
                     } else {
                         othm::start(L, white ? b.y : b.x, white ? b.x : b.y, a.depth);
+                        othm::order_reset(Q);
                         idx = g;
                     }
                 }
             }
         }
         if (L.depth >= 0) {
-            othm::advance<DeviceRules>(L, stk, table, a.limit);
+            if constexpr (kOrdered)
+                othm::advance_ordered<DeviceRules, true>(L, Q, stk, table, a.limit);
+            else
+                othm::advance<DeviceRules>(L, stk, table, a.limit);
             if (L.depth < 0) emit(a, idx, L.value, L.best_mv, L.status, L.nodes);
         }
     }
 }
+
+__global__ __launch_bounds__(kSearchBlock) void search_kernel(SearchArgs a) { search_body<false>(a); }
+__global__ __launch_bounds__(kSearchBlock) void search_ordered_kernel(SearchArgs a) { search_body<true>(a); }
 
 inline int status_of(hipError_t e) { return e == hipSuccess ? OTH_OK : -(int)e; }
 
@@ -159,28 +177,30 @@ int env_int(const char* name, int dflt) {
     return v && *v ? atoi(v) : dflt;
 }
 
-// blocks of the search kernel a device holds at once, resolved on first use
+// blocks of the search kernel (order 0) or the ordered one (1) a device holds at
+// once, resolved on first use
 constexpr int kMaxDevices = 64;
-std::atomic<int> g_resident[kMaxDevices];
+std::atomic<int> g_resident[2][kMaxDevices];
 
-int resident_blocks() {
+int resident_blocks(int order) {
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= kMaxDevices) return -1;
-    int r = g_resident[dev].load(std::memory_order_acquire);
+    int r = g_resident[order][dev].load(std::memory_order_acquire);
     if (r > 0) return r;
     int cus = 256, per_cu = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(search_kernel),
-                                                       kSearchBlock, 0);
+    const void* kernel = order ? reinterpret_cast<const void*>(search_ordered_kernel)
+                               : reinterpret_cast<const void*>(search_kernel);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kSearchBlock, 0);
     (void)hipGetLastError();
     r = std::max(cus, 1) * (per_cu > 0 ? per_cu : 4);
-    g_resident[dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
+    g_resident[order][dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
     return r;
 }
 
-int search_grid(int64_t n) {
-    const int resident = resident_blocks();
+int search_grid(int64_t n, int order) {
+    const int resident = resident_blocks(order);
     if (resident <= 0) return -1;
     const int cap = std::min(std::max(env_int("OTH_SEARCH_BLOCKS", resident), 1), resident);
     return (int)std::min<int64_t>((n + kSearchBlock - 1) / kSearchBlock, (int64_t)cap);
@@ -190,12 +210,13 @@ int search_grid(int64_t n) {
 
 extern "C" {
 
-int othm_search(const uint64_t* boards, const uint8_t* turn, int depth, const int8_t* weights, uint32_t node_limit,
-                int32_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes, uint64_t* work, int64_t n,
-                void* stream) {
+int otho_search_ordered(const uint64_t* boards, const uint8_t* turn, int depth, int order, const int8_t* weights,
+                        uint32_t node_limit, int32_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes,
+                        uint64_t* work, int64_t n, void* stream) {
+    if (order < 0 || order > OTHO_MAX_ORDER) return OTH_EINVAL;
     if (n < 0 || !work || !weights || depth < 1 || depth > OTHM_MAX_DEPTH || (n > 0 && !boards)) return OTH_EINVAL;
     if (n == 0) return OTH_OK;
-    const int grid = search_grid(n);
+    const int grid = search_grid(n, order);
     if (grid <= 0) return status_of(hipErrorInvalidDevice);
     SearchArgs a;
     a.boards = boards;
@@ -210,15 +231,27 @@ int othm_search(const uint64_t* boards, const uint8_t* turn, int depth, const in
     a.limit = node_limit ? node_limit : OTHM_DEFAULT_NODE_LIMIT;
     a.depth = depth;
     for (int k = 0; k < OTH_EVAL_WEIGHTS; k++) a.w[k] = weights[k];
-    search_kernel<<<(unsigned)grid, kSearchBlock, 0, (hipStream_t)stream>>>(a);
+    if (order)
+        search_ordered_kernel<<<(unsigned)grid, kSearchBlock, 0, (hipStream_t)stream>>>(a);
+    else
+        search_kernel<<<(unsigned)grid, kSearchBlock, 0, (hipStream_t)stream>>>(a);
     return status_of(hipGetLastError());
 }
 
-int othm_search_grid(int64_t n) {
-    if (n < 0) return OTH_EINVAL;
+int othm_search(const uint64_t* boards, const uint8_t* turn, int depth, const int8_t* weights, uint32_t node_limit,
+                int32_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes, uint64_t* work, int64_t n,
+                void* stream) {
+    return otho_search_ordered(boards, turn, depth, 0, weights, node_limit, value, best_move, status, nodes, work, n,
+                               stream);
+}
+
+int otho_search_ordered_grid(int64_t n, int order) {
+    if (order < 0 || order > OTHO_MAX_ORDER || n < 0) return OTH_EINVAL;
     if (n == 0) return 0;
-    const int grid = search_grid(n);
+    const int grid = search_grid(n, order);
     return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
 }
+
+int othm_search_grid(int64_t n) { return otho_search_ordered_grid(n, 0); }
 
 }  // extern "C"

@@ -135,6 +135,9 @@ OTHM_FN void apply_score(Lane& L, int score) {
     }
 }
 
+// (pop() and advance() have twins in order_core.hpp, pop_ordered() and
+// advance_ordered(): the same transitions with another choice of the next move.
+// A change to the leaf, pass, game-over or push code here belongs there too.)
 // POP: the current frame is done (M == 0, checked), its value is alpha
 template <class S>
 OTHM_FN void pop(Lane& L, S& stk) {

@@ -15,6 +15,10 @@
 //      the task ends and folds the result into the tree; the lane that
 //      completes the root emits the position's answer.
 //
+// With order = 1 (include/othello_order.h) the third launch is
+// task_ordered_kernel: the same loop around order_core.hpp's advance_ordered()
+// with the root tie rule off; the expansion is the same in both orders.
+//
 // What one block writes and another reads inside the task launch is the state
 // word of a node and the position's node counter, both touched by agent-scope
 // atomics only; the immutable node fields cross a kernel boundary.  No lane
@@ -30,7 +34,9 @@
 #include "../../include/othello.h"
 #include "../../include/othello_search.h"
 #include "../../include/othello_tree.h"
+#include "../../include/othello_order.h"
 #include "bitboard.hpp"
+#include "order_core.hpp"
 #include "tree_core.hpp"
 
 static_assert(OTHT_MAX_SPLIT == otht::kMaxSplit && OTHT_NOROOM == otht::kNoRoom && OTHT_MIN_NODES == otht::kMinNodes,
@@ -302,6 +308,7 @@ struct TaskArgs {
     int8_t w[OTH_EVAL_WEIGHTS];
 };
 
+// (task_ordered_kernel below is this loop again with the ordered machine: a change here belongs there too)
 __global__ __launch_bounds__(kTaskBlock) void task_kernel(TaskArgs a) {
     __shared__ u32 frames[othm::kFrames * othm::kFields * kTaskBlock];
     __shared__ int table[othm::kEvalTable];
@@ -384,6 +391,95 @@ __global__ __launch_bounds__(kTaskBlock) void task_kernel(TaskArgs a) {
     }
 }
 
+// task_kernel with order_core.hpp's machine inside a task (otho_tree_ordered,
+// order = 1): the same loop, the scoring state Q beside the lane's L, the root
+// tie rule off (a task's depth-0 frame is a tree node).  Kept as
+// a kernel of its own text so that task_kernel compiles to what it always was.
+__global__ __launch_bounds__(kTaskBlock) void task_ordered_kernel(TaskArgs a) {
+    __shared__ u32 frames[othm::kFrames * othm::kFields * kTaskBlock];
+    __shared__ int table[othm::kEvalTable];
+    const u32 lane = threadIdx.x;
+    if (lane < (u32)othm::kEvalTable) othm::widen_weight(a.w, (int)lane, table);
+    __syncthreads();
+    const u64 ntasks = a.s.tbase[a.n];
+    const u64 total = ntasks + a.lanes;
+    LdsStack stk{frames + lane};
+    othm::Lane L;
+    L.depth = -1;
+    othm::Order Q;
+    othm::order_reset(Q);
+    u64 pos = 0;
+    u32 node = 0;
+    bool exhausted = false;  // the lane has made its failing request
+    for (;;) {
+        const bool idle = L.depth < 0;
+        const bool want = idle && !exhausted;
+        const u64 wantm = __ballot(want);
+        const u64 busym = __ballot(!idle);
+        if ((wantm | busym) == 0) break;
+        const u64 cnt = (u64)__popcll(wantm);
+        bool done = false;  // the lane's task ended in this turn of the loop
+        int v = 0;
+        u64 lim = 0;
+        u32 spent = 0;
+        if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
+            u64 base = 0;
+            if (lane == 0) {
+                base = atomicAdd(a.work, cnt);
+                if (base + cnt == total) atomicExch(a.work, 0ull);  // every request is made: reset
+            }
+            base = __shfl(base, 0);
+            if (want) {
+                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
+                if (g >= ntasks) {
+                    exhausted = true;
+                } else {
+                    u64 lo = 0, hi = a.n;  // the last position whose first task is <= g
+                    while (hi - lo > 1) {
+                        const u64 mid = (lo + hi) >> 1;
+                        if (a.s.tbase[mid] <= g) lo = mid; else hi = mid;
+                    }
+                    pos = lo;
+                    node = a.s.tasks[pos * a.npp + (g - a.s.tbase[pos])];
+                    Node* slab = a.s.nodes + pos * a.npp;
+                    int alpha, beta;
+                    otht::window<DeviceAtomics>(slab, node, kShareBounds, alpha, beta);
+                    if (alpha >= beta) {  // cut off before it began: it reports its beta
+                        done = true;
+                        v = beta;
+                    } else {
+                        otht::start_task(L, slab[node], alpha, beta);
+                        othm::order_reset(Q);
+                    }
+                }
+            }
+        }
+        if (L.depth >= 0) {
+            othm::advance_ordered<DeviceRules, false>(L, Q, stk, table, a.limit);
+            if (L.depth < 0) {
+                done = true;
+                v = L.value;
+                lim = L.status == othm::kLimit ? otht::kLimitBit : 0ull;
+                spent = L.nodes;
+            }
+        }
+        if (done) {
+            Node* slab = a.s.nodes + pos * a.npp;
+            PosHdr* hdr = a.s.hdr + pos;
+            const u64 before = __hip_atomic_fetch_add(&hdr->nodes, (unsigned long long)spent, __ATOMIC_RELAXED,
+                                                      __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("" ::"v"(before) : "memory");
+            if (otht::fold_up<DeviceAtomics>(slab, node, v, lim)) {
+                int value;
+                u32 mv, st;
+                otht::root_result<DeviceAtomics>(slab, value, mv, st);
+                emit(a.out, pos, value, mv, st,
+                     __hip_atomic_load(&hdr->nodes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            }
+        }
+    }
+}
+
 inline int status_of(hipError_t e) { return e == hipSuccess ? OTH_OK : -(int)e; }
 
 int env_int(const char* name, int dflt) {
@@ -391,28 +487,30 @@ int env_int(const char* name, int dflt) {
     return v && *v ? atoi(v) : dflt;
 }
 
-// blocks of the task kernel a device holds at once, resolved on first use
+// blocks of the task kernel (order 0) or the ordered one (1) a device holds at
+// once, resolved on first use
 constexpr int kMaxDevices = 64;
-std::atomic<int> g_resident[kMaxDevices];
+std::atomic<int> g_resident[2][kMaxDevices];
 
-int resident_blocks() {
+int resident_blocks(int order) {
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (dev < 0 || dev >= kMaxDevices) return -1;
-    int r = g_resident[dev].load(std::memory_order_acquire);
+    int r = g_resident[order][dev].load(std::memory_order_acquire);
     if (r > 0) return r;
     int cus = 256, per_cu = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(task_kernel), kTaskBlock,
-                                                       0);
+    const void* kernel = order ? reinterpret_cast<const void*>(task_ordered_kernel)
+                               : reinterpret_cast<const void*>(task_kernel);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kTaskBlock, 0);
     (void)hipGetLastError();
     r = std::max(cus, 1) * (per_cu > 0 ? per_cu : 4);
-    g_resident[dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
+    g_resident[order][dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
     return r;
 }
 
-int task_grid(int64_t tasks) {
-    const int resident = resident_blocks();
+int task_grid(int64_t tasks, int order) {
+    const int resident = resident_blocks(order);
     if (resident <= 0) return -1;
     const int cap = std::min(std::max(env_int("OTH_SEARCH_BLOCKS", resident), 1), resident);
     return (int)std::min<int64_t>(std::max<int64_t>((tasks + kTaskBlock - 1) / kTaskBlock, 1), (int64_t)cap);
@@ -434,10 +532,11 @@ int64_t otht_scratch_bytes(int64_t n, int32_t nodes_per_position) {
     return scratch_layout(n, nodes_per_position, nullptr, nullptr);
 }
 
-int otht_search(const uint64_t* boards, const uint8_t* turn, int depth, int split, const int8_t* weights,
-                uint32_t node_limit, int32_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes,
-                void* scratch, int64_t scratch_bytes, int32_t nodes_per_position, uint64_t* work, int64_t n,
-                void* stream) {
+int otho_tree_ordered(const uint64_t* boards, const uint8_t* turn, int depth, int split, int order,
+                      const int8_t* weights, uint32_t node_limit, int32_t* value, uint8_t* best_move, uint8_t* status,
+                      uint32_t* nodes, void* scratch, int64_t scratch_bytes, int32_t nodes_per_position,
+                      uint64_t* work, int64_t n, void* stream) {
+    if (order < 0 || order > OTHO_MAX_ORDER) return OTH_EINVAL;
     if (n < 0 || n > 0x7FFFFFFF || !work || !weights || (n > 0 && !boards)) return OTH_EINVAL;
     if (split < 1 || split > OTHT_MAX_SPLIT || depth <= split || depth > split + OTHM_MAX_DEPTH) return OTH_EINVAL;
     const int64_t total_nodes = slab_nodes(n, nodes_per_position);
@@ -448,7 +547,7 @@ int otht_search(const uint64_t* boards, const uint8_t* turn, int depth, int spli
     // a position has at most 33^split tasks, and no more than its slab holds
     int64_t per = 1;
     for (int k = 0; k < split; k++) per = std::min<int64_t>(per * 33, nodes_per_position);
-    const int grid = task_grid(n * per);
+    const int grid = task_grid(n * per, order);
     if (grid <= 0) return status_of(hipErrorInvalidDevice);
     hipStream_t st = (hipStream_t)stream;
     Outputs out{value, best_move, status, nodes};
@@ -475,15 +574,28 @@ int otht_search(const uint64_t* boards, const uint8_t* turn, int depth, int spli
     t.npp = (u32)nodes_per_position;
     t.limit = node_limit ? node_limit : OTHM_DEFAULT_NODE_LIMIT;
     for (int k = 0; k < OTH_EVAL_WEIGHTS; k++) t.w[k] = weights[k];
-    task_kernel<<<(unsigned)grid, kTaskBlock, 0, st>>>(t);
+    if (order)
+        task_ordered_kernel<<<(unsigned)grid, kTaskBlock, 0, st>>>(t);
+    else
+        task_kernel<<<(unsigned)grid, kTaskBlock, 0, st>>>(t);
     return status_of(hipGetLastError());
 }
 
-int otht_search_grid(int64_t tasks) {
-    if (tasks < 0) return OTH_EINVAL;
+int otht_search(const uint64_t* boards, const uint8_t* turn, int depth, int split, const int8_t* weights,
+                uint32_t node_limit, int32_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes,
+                void* scratch, int64_t scratch_bytes, int32_t nodes_per_position, uint64_t* work, int64_t n,
+                void* stream) {
+    return otho_tree_ordered(boards, turn, depth, split, 0, weights, node_limit, value, best_move, status, nodes,
+                               scratch, scratch_bytes, nodes_per_position, work, n, stream);
+}
+
+int otho_tree_ordered_grid(int64_t tasks, int order) {
+    if (order < 0 || order > OTHO_MAX_ORDER || tasks < 0) return OTH_EINVAL;
     if (tasks == 0) return 0;
-    const int grid = task_grid(tasks);
+    const int grid = task_grid(tasks, order);
     return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
 }
+
+int otht_search_grid(int64_t tasks) { return otho_tree_ordered_grid(tasks, 0); }
 
 }  // extern "C"

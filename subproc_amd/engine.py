@@ -37,7 +37,9 @@ ops.search's, a fixed-depth alpha-beta with the eval table at the horizon (one
 launch per ``go``; depth 1 is the "eval" policy's move).  ``--solve-empties``
 still takes precedence where it applies.  ``--split S`` (S = 1..4) makes that
 search the split search (ops.search(split=S)): the position's tree is spread
-over the whole device, and D may go to 8 + S.
+over the whole device, and D may go to 8 + S.  ``--order 1`` searches with move
+ordering (ops.search(order=1), include/othello_order.h): the same moves from a
+smaller tree.
 """
 import argparse
 import random
@@ -52,14 +54,17 @@ from .codec import handstr_from_coord
 
 
 class Engine:
-    def __init__(self, name="GPU", policy="greedy", seed=0, weights=None, solve_empties=0, depth=1, split=0):
+    def __init__(self, name="GPU", policy="greedy", seed=0, weights=None, solve_empties=0, depth=1, split=0, order=0):
         if not 0 <= solve_empties <= _lib.SOLVE_MAX_EMPTIES:
             raise ValueError(f"solve_empties must lie in 0..{_lib.SOLVE_MAX_EMPTIES}")
         if not 0 <= split <= _lib.TREE_MAX_SPLIT:
             raise ValueError(f"split must lie in 0..{_lib.TREE_MAX_SPLIT}")
         if not 1 <= depth <= _lib.SEARCH_MAX_DEPTH + split:
             raise ValueError(f"depth must lie in 1..{_lib.SEARCH_MAX_DEPTH + split}")
+        if not 0 <= order <= _lib.ORDER_MAX:
+            raise ValueError(f"order must lie in 0..{_lib.ORDER_MAX}")
         self.solve_empties = solve_empties
+        self.order = order
         self.depth = depth
         # (a depth the split leaves no plies below is searched unsplit)
         self.split = split if depth > split else 0
@@ -124,7 +129,8 @@ class Engine:
         dev = torch.device("cuda", torch.cuda.current_device())
         boards = ops.from_numpy_u64(np.array([[bl, wh]], np.uint64), dev)
         side = torch.full((1,), b.turn, dtype=torch.uint8, device=dev)
-        r = ops.search(boards, side, self.depth, weights=self.weights, node_limit=1 << 24, split=self.split)
+        r = ops.search(boards, side, self.depth, weights=self.weights, node_limit=1 << 24, split=self.split,
+                       order=self.order)
         sq = int(r.best_move.cpu()[0])
         if int(r.status.cpu()[0]) != _lib.SEARCH_SEARCHED or sq > 63:
             return None
@@ -165,7 +171,8 @@ class Engine:
         elif cmd == "verbose p":
             extra = " weights=%s" % self.weights.reshape(-1).tolist() if self.policy in ("eval", "search") else ""
             if self.policy == "search":
-                extra = " depth=%d" % self.depth + (" split=%d" % self.split if self.split > 0 else "") + extra
+                extra = " depth=%d" % self.depth + (" split=%d" % self.split if self.split > 0 else "") + (
+                    " order=%d" % self.order if self.order > 0 else "") + extra
             if self.solve_empties > 0:
                 extra += " solve_empties=%d" % self.solve_empties
             out("%s policy=%s%s" % (self.name, self.policy, extra))
@@ -206,11 +213,13 @@ def main(argv=None):
     p.add_argument("--depth", type=int, default=1, metavar="D", help="plies policy search looks ahead (1..8, with --split S 1..8+S)")
     p.add_argument("--split", type=int, default=0, metavar="S",
                    help="spread policy search's tree over the device: its top S plies become tasks (0 = off, max 4)")
+    p.add_argument("--order", type=int, choices=[0, 1], default=0,
+                   help="policy search's move ordering: 0 lowest square first, 1 ordered (same moves, smaller tree)")
     p.add_argument("--solve-empties", type=int, default=0, metavar="K",
                    help="play the exact solver's move once at most K squares are empty (0 = never, max 12)")
     a = p.parse_args(argv)
     weights = params.read_paramgen(a.params)[1] if a.params else None
-    eng = Engine(a.name, a.policy, a.seed, weights, a.solve_empties, a.depth, a.split)
+    eng = Engine(a.name, a.policy, a.seed, weights, a.solve_empties, a.depth, a.split, a.order)
 
     def out(s):
         sys.stdout.write(s + "\n")

@@ -68,12 +68,14 @@ class VecEnv:
         that achieves it, for the games with at most `max_empties` empties."""
         return ops.solve(self.boards, self.turn, max_empties=max_empties, node_limit=node_limit)
 
-    def search(self, depth, weights=None, node_limit=0, split=0):
+    def search(self, depth, weights=None, node_limit=0, split=0, order=0):
         """Depth-limited search of the current state (ops.search): per game the
         `depth`-ply alpha-beta value under the eval table `weights` from the
         mover's side and the move that achieves it.  `split` >= 1: the split
-        search, for a few games at a time and depths up to 8 + split."""
-        return ops.search(self.boards, self.turn, depth, weights=weights, node_limit=node_limit, split=split)
+        search, for a few games at a time and depths up to 8 + split; `order` = 1 the
+        ordered search (the same results from a smaller tree)."""
+        return ops.search(self.boards, self.turn, depth, weights=weights, node_limit=node_limit, split=split,
+                          order=order)
 
     def books(self):
         """Book text (serialize_str, board.py:214-221) of every game: oth_book_text

@@ -463,7 +463,7 @@ SearchResult = namedtuple("SearchResult", "value best_move status nodes")
 
 
 def search(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, work=None, split=0,
-           nodes_per_position=_lib.TREE_DEFAULT_NODES):
+           nodes_per_position=_lib.TREE_DEFAULT_NODES, order=0):
     """Depth-limited alpha-beta search (othm_search, include/othello_search.h):
     every position is searched ``depth`` (1..8) plies deep for its mover (White
     if turn == 2, else Black) with the linear eval of ``weights`` (int8 [4, 9],
@@ -494,6 +494,13 @@ def search(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, wo
     ``nodes`` then depends on timing.  It pays for small batches, down to one
     position.  The scratch (otht_scratch_bytes) is allocated here, so this
     form does not run under graph capture.
+
+    ``order`` = 1 searches with move ordering (otho_search_ordered /
+    otho_tree_ordered, include/othello_order.h): value, best_move and status
+    are those of ``order`` = 0, ties included, from a smaller tree; ``nodes``
+    then counts the ordering's scoring placements too, and only a position
+    within reach of ``node_limit`` may end differently.  With ``split`` the
+    searches inside the tasks are ordered, the tree's expansion is not.
     """
     n = _n(boards)
     capturing = torch.cuda.is_current_stream_capturing()
@@ -504,7 +511,7 @@ def search(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, wo
         raise ValueError("node_limit must fit 32 bits")
     if int(split) != 0:
         return _search_split(boards, turn, n, int(depth), int(split), weights, int(node_limit), want_nodes, work,
-                             int(nodes_per_position), capturing)
+                             int(nodes_per_position), capturing, int(order))
     d = boards.device
     pb = _dev(boards, "boards", torch.int64)
     pt = _dev(turn, "turn", torch.uint8, (n,), d)
@@ -514,21 +521,24 @@ def search(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, wo
     nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
     w = work_word(d) if work is None else work
     pw = _dev(w, "work", torch.int64, (1,), d)
+    lib = _lib.load()
+    fn, name, ordered = (lib.otho_search_ordered, "otho_search_ordered", (int(order),)) if int(order) != 0 else (
+        lib.othm_search, "othm_search", ())
     with torch.cuda.device(d):
-        rc = _lib.load().othm_search(pb, pt, int(depth), _weights_ptr(weights), int(node_limit), val.data_ptr(),
-                                     mv.data_ptr(), st.data_ptr(), None if nd is None else nd.data_ptr(), pw, n,
-                                     _stream())
+        rc = fn(pb, pt, int(depth), *ordered, _weights_ptr(weights), int(node_limit), val.data_ptr(), mv.data_ptr(),
+                st.data_ptr(), None if nd is None else nd.data_ptr(), pw, n, _stream())
         if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
             if work is None:
                 _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
             elif not capturing:
                 w.zero_()
-        check(rc, "othm_search")
+        check(rc, name)
     return SearchResult(val, mv, st, nd)
 
 
-def _search_split(boards, turn, n, depth, split, weights, node_limit, want_nodes, work, nodes_per_position, capturing):
-    """:func:`search` with split >= 1: otht_search on a scratch of its own."""
+def _search_split(boards, turn, n, depth, split, weights, node_limit, want_nodes, work, nodes_per_position, capturing,
+                  order=0):
+    """:func:`search` with split >= 1: otht_search (otho_tree_ordered with order != 0) on a scratch of its own."""
     if capturing:
         raise RuntimeError("ops.search(split >= 1) allocates its scratch and does not run under graph capture")
     if not -2**31 <= nodes_per_position < 2**31:
@@ -547,16 +557,18 @@ def _search_split(boards, turn, n, depth, split, weights, node_limit, want_nodes
     scratch = torch.empty(max(int(size), 8) // 8, dtype=torch.int64, device=d)
     w = work_word(d) if work is None else work
     pw = _dev(w, "work", torch.int64, (1,), d)
+    fn, name, ordered = (lib.otho_tree_ordered, "otho_tree_ordered", (order,)) if order != 0 else (
+        lib.otht_search, "otht_search", ())
     with torch.cuda.device(d):
-        rc = lib.otht_search(pb, pt, depth, split, _weights_ptr(weights), node_limit, val.data_ptr(), mv.data_ptr(),
-                             st.data_ptr(), None if nd is None else nd.data_ptr(), scratch.data_ptr(),
-                             scratch.numel() * 8, nodes_per_position, pw, n, _stream())
+        rc = fn(pb, pt, depth, split, *ordered, _weights_ptr(weights), node_limit, val.data_ptr(), mv.data_ptr(),
+                st.data_ptr(), None if nd is None else nd.data_ptr(), scratch.data_ptr(), scratch.numel() * 8,
+                nodes_per_position, pw, n, _stream())
         if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
             if work is None:
                 _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
             else:
                 w.zero_()
-        check(rc, "otht_search")
+        check(rc, name)
     # (the caching allocator hands the scratch to later work of THIS stream only)
     return SearchResult(val, mv, st, nd)
 
@@ -566,7 +578,7 @@ PlayResult = namedtuple("PlayResult", "final_boards diff plies moves hist a_blac
 
 def play(n, seed, game_id0=0, weights_a=None, weights_b=None, depth_a=1, depth_b=None, exact_empties=0, n_rand_a=0,
          n_rand_b=0, swap_colours=False, start=None, start_turn=None, record_moves=False, node_limit=0,
-         want_nodes=False, hist=None, device="cuda", work=None):
+         want_nodes=False, hist=None, device="cuda", work=None, order=0):
     """n whole games between two searching players in one launch (othp_play,
     include/othello_play.h): :func:`rollout_runner`'s match schedule -- player
     A against player B, the colour draw, the random-move budgets -- with every
@@ -587,7 +599,9 @@ def play(n, seed, game_id0=0, weights_a=None, weights_b=None, depth_a=1, depth_b
     (int64, with ``want_nodes``) is the sum of each game's search nodes.
 
     One lane plays one game: a launch lasts as long as its longest game.
-    ``work`` as in :func:`rollout`."""
+    ``work`` as in :func:`rollout`.  ``order`` = 1: both players search with
+    move ordering (otho_play_ordered, include/othello_order.h); the games are
+    the same move for move, ``nodes`` is smaller."""
     capturing = torch.cuda.is_current_stream_capturing()
     if work is None and capturing:
         raise RuntimeError("ops.play under graph capture needs an explicit work word: an int64 (1,) device "
@@ -613,19 +627,21 @@ def play(n, seed, game_id0=0, weights_a=None, weights_b=None, depth_a=1, depth_b
     ph = _dev(hist, "hist", torch.int64, (HIST_BINS,), d)
     w = work_word(d) if work is None else work
     pw = _dev(w, "work", torch.int64, (1,), d)
+    lib = _lib.load()
+    fn, name, ordered = (lib.otho_play_ordered, "otho_play_ordered", (int(order),)) if int(order) != 0 else (
+        lib.othp_play, "othp_play", ())
     with torch.cuda.device(d):
-        rc = _lib.load().othp_play(ps, pst, seed & (2**64 - 1), game_id0, _weights_ptr(weights_a),
-                                   _weights_ptr(weights_b), int(depth_a), int(depth_a if depth_b is None else depth_b),
-                                   int(exact_empties), int(n_rand_a), int(n_rand_b), int(bool(swap_colours)),
-                                   int(node_limit), ab.data_ptr(), fb.data_ptr(), df.data_ptr(), pl.data_ptr(),
-                                   None if mv is None else mv.data_ptr(), st.data_ptr(),
-                                   None if nd is None else nd.data_ptr(), ph, pw, n, _stream())
+        rc = fn(ps, pst, seed & (2**64 - 1), game_id0, _weights_ptr(weights_a), _weights_ptr(weights_b), int(depth_a),
+                int(depth_a if depth_b is None else depth_b), int(exact_empties), *ordered, int(n_rand_a),
+                int(n_rand_b), int(bool(swap_colours)), int(node_limit), ab.data_ptr(), fb.data_ptr(), df.data_ptr(),
+                pl.data_ptr(), None if mv is None else mv.data_ptr(), st.data_ptr(),
+                None if nd is None else nd.data_ptr(), ph, pw, n, _stream())
         if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
             if work is None:
                 _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
             elif not capturing:
                 w.zero_()
-        check(rc, "othp_play")
+        check(rc, name)
     return PlayResult(fb, df, pl, mv, hist, ab, st, nd)
 
 

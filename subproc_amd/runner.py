@@ -51,12 +51,13 @@ def hamlet_param_line(name, policy, weights, depth=None, solve_empties=0):
 
 def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, policy="eval", name_a="Hamlet",
                name_b="GPU", device="cuda", record=True, win_rule="reference", store=None, depth=None,
-               exact_empties=0):
+               exact_empties=0, order=0):
     """n GameRunner games between A (``weights_a``) and B (``weights_b``,
     default params.DEFAULT_WEIGHTS), both playing ``policy``: "greedy", "eval",
     or "search" -- every policy move searched ``depth`` plies deep (an int, or
     (A's, B's); 1..8) over the mover's table, exactly from ``exact_empties``
-    empty squares on (ops.play: the whole games in one launch).  A "search"
+    empty squares on (ops.play: the whole games in one launch; ``order`` = 1: with
+    move ordering, the same games from smaller trees).  A "search"
     game that a search's node limit stopped (ops.play's status) raises.
 
     Game i is global id ``game_id0 + i`` (its book id).  ``record=True``
@@ -75,7 +76,7 @@ def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, po
             raise ValueError("policy 'search' needs depth=D or depth=(Da, Db)")
         depth_a, depth_b = (depth, depth) if isinstance(depth, int) else depth
         r = ops.play(n, seed, game_id0, wa, wb, depth_a, depth_b, exact_empties, n_rand_a, n_rand_b, swap,
-                     record_moves=record, device=device)
+                     record_moves=record, device=device, order=order)
         if not bool((r.status == ops._lib.SEARCH_SEARCHED).all()):
             raise RuntimeError("do_matches: a game's search reached the node limit")
         line = {"a": hamlet_param_line(name_a, policy, wa, depth_a, exact_empties),
@@ -83,6 +84,8 @@ def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, po
     else:
         if depth is not None or exact_empties:
             raise ValueError("depth and exact_empties apply to policy 'search' only")
+        if order:
+            raise ValueError("order applies to policy 'search' only")
         r = ops.rollout_runner(n, seed, game_id0, policy, wa, wb, n_rand_a, n_rand_b, swap, record_moves=record,
                                device=device)
         line = {"a": hamlet_param_line(name_a, policy, wa), "b": hamlet_param_line(name_b, policy, wb)}

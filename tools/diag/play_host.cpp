@@ -9,7 +9,8 @@
 //   * the CPU context line of tools/play_bench.py (16 threads).
 //
 // build:  g++ -O2 -std=c++17 -fopenmp -o tools/diag/play_host tools/diag/play_host.cpp
-// run:    play_host ARGS OUT [threads=16]
+// run:    play_host ARGS OUT [threads=16] [order=0]
+//   order 1: order_core.hpp's ordered machine in every search (include/othello_order.h)
 //   ARGS: a text file,
 //           line 1: n seed game_id0 depth_a depth_b exact_empties n_rand_a n_rand_b swap node_limit have_start
 //           line 2: A's 36 weights, line 3: B's 36 weights (integers -128..127)
@@ -85,13 +86,18 @@ struct Out {
     }
 };
 
-static void play_one(const Start& s, u64 key, const othp::Match& m, const int* tables, Out& out) {
+static void play_one(const Start& s, u64 key, const othp::Match& m, const int* tables, int order, Out& out) {
     memset(out.moves, 255, sizeof out.moves);
     othp::Game G;
     othm::Lane L;
     HostStack stk;
     othp::begin(G, L, m, key, s.black, s.white, s.turn == 2);
-    while (G.live) othp::advance<HostRules>(G, L, stk, tables, m, out);
+    othm::Order Q;
+    othm::order_reset(Q);
+    if (order)
+        while (G.live) othp::advance_ordered<HostRules>(G, L, Q, stk, tables, m, out);
+    else
+        while (G.live) othp::advance<HostRules>(G, L, stk, tables, m, out);
     out.a_black = G.a_black;
     out.black = othp::black_of(G);
     out.white = othp::white_of(G);
@@ -112,11 +118,12 @@ static bool read_weights(FILE* f, int8_t* w36) {
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s ARGS OUT [threads]\n", argv[0]);
+        fprintf(stderr, "usage: %s ARGS OUT [threads] [order]\n", argv[0]);
         return 2;
     }
     const int threads = argc > 3 ? atoi(argv[3]) : 16;
-    if (threads < 1) return 2;
+    const int order = argc > 4 ? atoi(argv[4]) : 0;
+    if (threads < 1 || order < 0 || order > 1) return 2;
     FILE* in = fopen(argv[1], "r");
     if (!in) return 1;
     long n;
@@ -154,7 +161,7 @@ int main(int argc, char** argv) {
     std::vector<Out> out((size_t)n);
     const auto t0 = std::chrono::steady_clock::now();
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
-    for (long i = 0; i < n; i++) play_one(starts[(size_t)i], othp::game_key(S, id0 + (u64)i), m, tables, out[(size_t)i]);
+    for (long i = 0; i < n; i++) play_one(starts[(size_t)i], othp::game_key(S, id0 + (u64)i), m, tables, order, out[(size_t)i]);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     FILE* o = fopen(argv[2], "w");
     if (!o) return 1;
@@ -169,8 +176,8 @@ int main(int argc, char** argv) {
     }
     fclose(o);
     fprintf(stderr,
-            "{\"games\": %ld, \"threads\": %d, \"depth_a\": %d, \"depth_b\": %d, \"seconds\": %.6f, "
+            "{\"games\": %ld, \"threads\": %d, \"depth_a\": %d, \"depth_b\": %d, \"order\": %d, \"seconds\": %.6f, "
             "\"games_per_s\": %.1f, \"plies\": %llu, \"nodes\": %llu}\n",
-            n, threads, da, db, sec, sec > 0 ? n / sec : 0.0, plies, nodes);
+            n, threads, da, db, order, sec, sec > 0 ? n / sec : 0.0, plies, nodes);
     return 0;
 }

@@ -9,7 +9,8 @@
 //   * the CPU context line of tools/search_bench.py (16 threads).
 //
 // build:  g++ -O2 -std=c++17 -fopenmp -o search_host tools/diag/search_host.cpp
-// run:    search_host IN OUT WEIGHTS depth [node_limit=0] [threads=16]
+// run:    search_host IN OUT WEIGHTS depth [node_limit=0] [threads=16] [order=0]
+//   order 1: order_core.hpp's ordered machine (include/othello_order.h)
 //   IN : one position per line, "<black hex> <white hex> <turn>"
 //   WEIGHTS: 36 integers in -128..127, [phase][feature]
 //   OUT: one line per position, "<value> <best_move> <status> <nodes>"
@@ -19,6 +20,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "../../subproc_amd/csrc/order_core.hpp"
 #include "../../subproc_amd/csrc/search_core.hpp"
 
 using othm::u32;
@@ -76,25 +78,31 @@ struct Out {
     u32 best, status, nodes;
 };
 
-static Out search_one(const Pos& p, int depth, const int* table, u32 limit) {
+static Out search_one(const Pos& p, int depth, const int* table, u32 limit, int order) {
     if (p.black & p.white) return Out{0, othm::kNoMove, othm::kInvalid, 0};
     othm::Lane L;
     HostStack stk;
     const bool white = p.turn == 2;
     othm::start(L, white ? p.white : p.black, white ? p.black : p.white, depth);
-    while (L.depth >= 0) othm::advance<HostRules>(L, stk, table, limit);
+    othm::Order Q;
+    othm::order_reset(Q);
+    if (order)
+        while (L.depth >= 0) othm::advance_ordered<HostRules, true>(L, Q, stk, table, limit);
+    else
+        while (L.depth >= 0) othm::advance<HostRules>(L, stk, table, limit);
     return Out{L.value, L.best_mv, L.status, L.nodes};
 }
 
 int main(int argc, char** argv) {
     if (argc < 5) {
-        fprintf(stderr, "usage: %s IN OUT WEIGHTS depth [node_limit] [threads]\n", argv[0]);
+        fprintf(stderr, "usage: %s IN OUT WEIGHTS depth [node_limit] [threads] [order]\n", argv[0]);
         return 2;
     }
     const int depth = atoi(argv[4]);
     const u32 limit_arg = argc > 5 ? (u32)strtoul(argv[5], nullptr, 0) : 0u;
     const int threads = argc > 6 ? atoi(argv[6]) : 16;
-    if (depth < 1 || depth > othm::kMaxDepth || threads < 1) return 2;
+    const int order = argc > 7 ? atoi(argv[7]) : 0;
+    if (depth < 1 || depth > othm::kMaxDepth || threads < 1 || order < 0 || order > 1) return 2;
     const u32 limit = limit_arg ? limit_arg : (1u << 28);
     FILE* wf = fopen(argv[3], "r");
     if (!wf) return 1;
@@ -118,7 +126,7 @@ int main(int argc, char** argv) {
     const auto t0 = std::chrono::steady_clock::now();
     const long n = (long)pos.size();
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
-    for (long i = 0; i < n; i++) out[i] = search_one(pos[i], depth, table, limit);
+    for (long i = 0; i < n; i++) out[i] = search_one(pos[i], depth, table, limit, order);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     FILE* o = fopen(argv[2], "w");
     if (!o) return 1;
@@ -129,8 +137,8 @@ int main(int argc, char** argv) {
     }
     fclose(o);
     fprintf(stderr,
-            "{\"positions\": %ld, \"threads\": %d, \"depth\": %d, \"seconds\": %.6f, \"positions_per_s\": %.1f, "
+            "{\"positions\": %ld, \"threads\": %d, \"depth\": %d, \"order\": %d, \"seconds\": %.6f, \"positions_per_s\": %.1f, "
             "\"nodes\": %llu}\n",
-            n, threads, depth, sec, sec > 0 ? n / sec : 0.0, nodes);
+            n, threads, depth, order, sec, sec > 0 ? n / sec : 0.0, nodes);
     return 0;
 }

@@ -13,7 +13,8 @@
 //
 // build:  g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all
 //             -o tools/diag/tree_host_asan tools/diag/tree_host.cpp
-// run:    tree_host IN OUT WEIGHTS depth split [nodes_per_position=32768] [node_limit=0] [seed=1]
+// run:    tree_host IN OUT WEIGHTS depth split [nodes_per_position=32768] [node_limit=0] [seed=1] [order=0]
+//   order 1: order_core.hpp's ordered machine inside the tasks, root tie rule off
 //   IN : one position per line, "<black hex> <white hex> <turn>"
 //   WEIGHTS: 36 integers in -128..127, [phase][feature]
 //   OUT: one line per position, four times "<value> <best_move> <status> <nodes>"
@@ -23,6 +24,7 @@
 #include <random>
 #include <vector>
 
+#include "../../subproc_amd/csrc/order_core.hpp"
 #include "../../subproc_amd/csrc/tree_core.hpp"
 
 using otht::Node;
@@ -98,7 +100,7 @@ enum Order { kForward, kReverse, kShuffle, kSnapshot };
 
 // tree.hip's expand_kernel and task_kernel for one position, one task at a time
 static Out search_one(const Pos& p, int depth, int split, u32 npp, const int* table, u32 limit, Order order,
-                      u32 seed) {
+                      u32 seed, int ordered) {
     if (p.black & p.white) return Out{0, othm::kNoMove, othm::kInvalid, 0};
     std::vector<Node> slab(npp);
     const bool white = p.turn == 2;
@@ -159,7 +161,12 @@ static Out search_one(const Pos& p, int depth, int split, u32 npp, const int* ta
             othm::Lane L;
             HostStack stk;
             otht::start_task(L, slab[t], alpha, beta);
-            while (L.depth >= 0) othm::advance<HostRules>(L, stk, table, limit);
+            othm::Order Q;
+            othm::order_reset(Q);
+            if (ordered)
+                while (L.depth >= 0) othm::advance_ordered<HostRules, false>(L, Q, stk, table, limit);
+            else
+                while (L.depth >= 0) othm::advance<HostRules>(L, stk, table, limit);
             v = L.value;
             lim = L.status == othm::kLimit ? otht::kLimitBit : 0;
             nodes += L.nodes;
@@ -177,13 +184,15 @@ static Out search_one(const Pos& p, int depth, int split, u32 npp, const int* ta
 
 int main(int argc, char** argv) {
     if (argc < 6) {
-        fprintf(stderr, "usage: %s IN OUT WEIGHTS depth split [nodes_per_position] [node_limit] [seed]\n", argv[0]);
+        fprintf(stderr, "usage: %s IN OUT WEIGHTS depth split [nodes_per_position] [node_limit] [seed] [order]\n", argv[0]);
         return 2;
     }
     const int depth = atoi(argv[4]), split = atoi(argv[5]);
     const long npp = argc > 6 ? atol(argv[6]) : 32768;
     const u32 limit_arg = argc > 7 ? (u32)strtoul(argv[7], nullptr, 0) : 0u;
     const u32 seed = argc > 8 ? (u32)strtoul(argv[8], nullptr, 0) : 1u;
+    const int ordered = argc > 9 ? atoi(argv[9]) : 0;
+    if (ordered < 0 || ordered > 1) return 2;
     if (split < 1 || split > otht::kMaxSplit || depth <= split || depth > split + othm::kMaxDepth ||
         npp < otht::kMinNodes || npp > (1 << 24))
         return 2;
@@ -210,7 +219,7 @@ int main(int argc, char** argv) {
     if (!o) return 1;
     for (const Pos& p : pos) {
         for (int order = 0; order < 4; order++) {
-            const Out r = search_one(p, depth, split, (u32)npp, table, limit, (Order)order, seed);
+            const Out r = search_one(p, depth, split, (u32)npp, table, limit, (Order)order, seed, ordered);
             fprintf(o, "%d %u %u %llu%s", r.value, r.best, r.status, (unsigned long long)r.nodes,
                     order == 3 ? "\n" : " ");
         }

@@ -84,7 +84,7 @@ def host_loop(b0, t0, moves, depths, limit):
     return b, wrong
 
 
-def host_line(a, n, source, depths, start, turn, nodes, ref):
+def host_line(a, n, source, depths, start, turn, nodes, ref, order=0):
     if not os.path.exists(HOST) or a.host_games <= 0:
         return {}
     import play_host_check as phc
@@ -98,7 +98,7 @@ def host_line(a, n, source, depths, start, turn, nodes, ref):
         phc.write_args(args, k, a.seed, 0, depths, 0, a.budgets if source == "open" else (0, 0), False, a.node_limit,
                        w, w, None if start is None else ops.to_numpy_u64(start[:k]),
                        None if turn is None else turn[:k].cpu().numpy())
-        r = subprocess.run([HOST, args, out, str(a.host_threads)], capture_output=True, text=True, check=True)
+        r = subprocess.run([HOST, args, out, str(a.host_threads), str(order)], capture_output=True, text=True, check=True)
         h = json.loads(r.stderr.strip().splitlines()[-1])
         got = phc.read_out(out)
     same = ((got["final_boards"] == ref["final_boards"][:k]).all() and (got["plies"] == ref["plies"][:k]).all()
@@ -122,6 +122,8 @@ def main():
     p.add_argument("--host-games", type=int, default=2048)
     p.add_argument("--host-nodes", type=float, default=4e8, help="host node budget per line")
     p.add_argument("--host-threads", type=int, default=16)
+    p.add_argument("--order", type=int, nargs="+", choices=[0, 1], default=[0],
+                   help="move ordering(s) of the kernel's searches, each a line (the host loop stays unordered)")
     a = p.parse_args()
     if a.node_limit <= 0:
         p.error("every launch carries a node limit")
@@ -133,10 +135,10 @@ def main():
     for source in a.sources:
         start, turn = (mid.boards, mid.turn) if source == "mid" else (None, None)
         budgets = tuple(a.budgets) if source == "open" else (0, 0)
-        for pair in a.depths:
+        for pair, order in [(p_, o) for p_ in a.depths for o in a.order]:
             depths = tuple(int(x) for x in pair.split(","))
             kw = dict(depth_a=depths[0], depth_b=depths[1], n_rand_a=budgets[0], n_rand_b=budgets[1], start=start,
-                      start_turn=turn, node_limit=a.node_limit)
+                      start_turn=turn, node_limit=a.node_limit, order=order)
             rec = ops.play(n, a.seed, record_moves=True, want_nodes=True, **kw)  # the games, and a warm-up
             torch.cuda.synchronize()
             ms, loop_ms, wrong = [], [], None
@@ -150,13 +152,13 @@ def main():
             nodes = rec.nodes.cpu().numpy().astype(np.int64)
             plies = rec.plies.cpu().numpy().astype(np.int64)
             status = rec.status.cpu().numpy()
-            line = {"source": source, "depths": list(depths), "budgets": list(budgets), "games": n,
+            line = {"source": source, "depths": list(depths), "order": order, "budgets": list(budgets), "games": n,
                     "ms_per_launch": med, "ms_all": ms, "games_per_s": n / (med * 1e-3),
                     "plies_per_s": int(plies.sum()) / (med * 1e-3), "nodes_per_s": int(nodes.sum()) / (med * 1e-3),
                     "plies_mean": float(plies.mean()), "game_nodes_mean": float(nodes.mean()),
                     "game_nodes_max": int(nodes.max()), "game_tail_ratio": float(nodes.max() / max(nodes.mean(), 1e-9)),
                     "limit_hits": int((status != SEARCHED).sum()), "node_limit": a.node_limit,
-                    "grid": _lib.load().othp_play_grid(n), "play_blocks": os.environ.get("OTH_PLAY_BLOCKS"),
+                    "grid": _lib.load().otho_play_ordered_grid(n, order), "play_blocks": os.environ.get("OTH_PLAY_BLOCKS"),
                     "library_sha16": _lib.library_sha16()}
             if loop_ms:
                 lmed = statistics.median(loop_ms)
@@ -165,7 +167,7 @@ def main():
                              "loop_finals_equal": bool(torch.equal(fb, rec.final_boards))})
             ref = {"final_boards": ops.to_numpy_u64(rec.final_boards).reshape(-1, 2), "plies": plies.astype(np.uint8),
                    "nodes": nodes.astype(np.uint64)}
-            line.update(host_line(a, n, source, depths, start, turn, nodes, ref))
+            line.update(host_line(a, n, source, depths, start, turn, nodes, ref, order))
             print(json.dumps(line), flush=True)
     return 0
 

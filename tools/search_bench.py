@@ -13,6 +13,8 @@ With tools/diag/search_host built (see its header), each line also carries the
 16-thread host figure on the first positions of the same set: --host-positions
 of them, fewer once their node count (known from the GPU run) would pass
 --host-nodes.  OTH_SEARCH_BLOCKS in the environment caps the grid (recorded).
+--order 0 1 runs every depth at each order in turn, in one process (order 1:
+include/othello_order.h; its nodes count the scoring placements too).
 
 --engine times one `go` of the Edax-protocol engine per depth instead (policy
 search at depths 1..6 beside policy eval), on --engine-positions midgame
@@ -38,7 +40,7 @@ from subproc_amd import _lib, codec, ops, params  # noqa: E402
 HOST = os.path.join(ROOT, "tools", "diag", "search_host")
 
 
-def host_line(boards, turn, depth, limit, threads):
+def host_line(boards, turn, depth, limit, threads, order=0):
     if not os.path.exists(HOST) or boards.shape[0] == 0:
         return {}
     b = ops.to_numpy_u64(boards)
@@ -50,7 +52,7 @@ def host_line(boards, turn, depth, limit, threads):
                 f.write("%x %x %d\n" % (int(bl), int(wh), int(tt)))
         with open(wts, "w") as f:
             f.write(" ".join(str(int(x)) for x in params.as_weights(params.DEFAULT_WEIGHTS).reshape(-1)))
-        r = subprocess.run([HOST, src, dst, wts, str(depth), str(limit), str(threads)], capture_output=True,
+        r = subprocess.run([HOST, src, dst, wts, str(depth), str(limit), str(threads), str(order)], capture_output=True,
                            text=True, check=True)
         h = json.loads(r.stderr.strip().splitlines()[-1])
         got = np.loadtxt(dst, dtype=np.int64).reshape(-1, 4)
@@ -64,8 +66,8 @@ def engine_times(a):
     pos = ops.sample_midgame(a.engine_positions, seed=a.seed)
     b = ops.to_numpy_u64(pos.boards)
     t = pos.turn.cpu().numpy()
-    for policy, depth in [("eval", 1)] + [("search", d) for d in a.depths if d <= 6]:
-        eng = engine.Engine(policy=policy, depth=depth)
+    for policy, depth, order in [("eval", 1, 0)] + [("search", d, o) for d in a.depths if d <= 6 for o in a.order]:
+        eng = engine.Engine(policy=policy, depth=depth, order=order)
         us = []
         for i in range(len(t)):
             text = codec.serialize_str(int(b[i, 0]), int(b[i, 1]), int(t[i]), True)
@@ -76,7 +78,7 @@ def engine_times(a):
             t0 = time.perf_counter()
             eng.choose()
             us.append((time.perf_counter() - t0) * 1e6)
-        print(json.dumps({"engine_policy": policy, "depth": depth if policy == "search" else None,
+        print(json.dumps({"engine_policy": policy, "depth": depth if policy == "search" else None, "order": order,
                           "positions": len(t), "us_per_go_median": statistics.median(us), "us_per_go_max": max(us),
                           "library_sha16": _lib.library_sha16()}), flush=True)
     return 0
@@ -93,6 +95,7 @@ def main():
     p.add_argument("--host-positions", type=int, default=2048)
     p.add_argument("--host-nodes", type=float, default=2e8, help="host node budget per depth")
     p.add_argument("--host-threads", type=int, default=16)
+    p.add_argument("--order", type=int, nargs="+", choices=[0, 1], default=[0], help="move ordering(s) to run")
     p.add_argument("--engine", action="store_true", help="time the engine's `go` per depth instead")
     p.add_argument("--engine-positions", type=int, default=64)
     a = p.parse_args()
@@ -103,31 +106,34 @@ def main():
     pos = ops.sample_midgame(a.positions, seed=a.seed)
     boards, turn = pos.boards, pos.turn
     n = boards.shape[0]
-    for depth in sorted(a.depths):
-        r = ops.search(boards, turn, depth, node_limit=a.node_limit, want_nodes=True)  # warm-up
+    stopped = set()
+    for depth, order in [(d, o) for d in sorted(a.depths) for o in a.order]:
+        if order in stopped:
+            continue
+        r = ops.search(boards, turn, depth, node_limit=a.node_limit, want_nodes=True, order=order)  # warm-up
         torch.cuda.synchronize()
         ms = []
         for _ in range(a.reps):
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
-            r = ops.search(boards, turn, depth, node_limit=a.node_limit, want_nodes=True)
+            r = ops.search(boards, turn, depth, node_limit=a.node_limit, want_nodes=True, order=order)
             t1.record()
             torch.cuda.synchronize()
             ms.append(t0.elapsed_time(t1))
         med = statistics.median(ms)
         nodes = r.nodes.cpu().numpy().view(np.uint32).astype(np.int64)
         status = r.status.cpu().numpy()
-        line = {"depth": depth, "positions": n, "ms_per_launch": med, "ms_all": ms,
+        line = {"depth": depth, "order": order, "positions": n, "ms_per_launch": med, "ms_all": ms,
                 "positions_per_s": n / (med * 1e-3), "nodes_per_s": int(nodes.sum()) / (med * 1e-3),
                 "nodes_mean": float(nodes.mean()), "nodes_max": int(nodes.max()),
                 "tail_ratio": float(nodes.max() / max(nodes.mean(), 1e-9)),
                 "limit_hits": int((status == _lib.SEARCH_LIMIT).sum()), "node_limit": a.node_limit,
-                "grid": _lib.load().othm_search_grid(n), "search_blocks": os.environ.get("OTH_SEARCH_BLOCKS"),
+                "grid": _lib.load().otho_search_ordered_grid(n, order), "search_blocks": os.environ.get("OTH_SEARCH_BLOCKS"),
                 "library_sha16": _lib.library_sha16()}
         k = min(n, a.host_positions)
         while k > 16 and nodes[:k].sum() > a.host_nodes:
             k //= 2
-        h = host_line(boards[:k], turn[:k], depth, a.node_limit, a.host_threads)
+        h = host_line(boards[:k], turn[:k], depth, a.node_limit, a.host_threads, order)
         rows = h.pop("_host_rows", None)
         if rows is not None:  # the same state machine: the two builds agree on everything
             same = ((rows[:, 0] == r.value[:k].cpu().numpy()) & (rows[:, 1] == r.best_move[:k].cpu().numpy())
@@ -136,9 +142,11 @@ def main():
         line.update(h)
         print(json.dumps(line), flush=True)
         if med > a.stop_ms:
-            print(json.dumps({"stopped_after_depth": depth, "reason": "launch took more than %.0f ms" % a.stop_ms}),
-                  flush=True)
-            break
+            print(json.dumps({"stopped_after_depth": depth, "order": order,
+                              "reason": "launch took more than %.0f ms" % a.stop_ms}), flush=True)
+            stopped.add(order)
+            if len(stopped) == len(set(a.order)):
+                break
     return 0
 
 

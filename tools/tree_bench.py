@@ -45,6 +45,7 @@ def main():
     p.add_argument("--nodes-per-position", type=int, default=_lib.TREE_DEFAULT_NODES)
     p.add_argument("--budget-s", type=float, default=20.0)
     p.add_argument("--lib", default=None, help="another build of the library")
+    p.add_argument("--order", type=int, nargs="+", choices=[0, 1], default=[0], help="move ordering(s), each a line")
     p.add_argument("--tag", default="shared", help="recorded on every line (shared / snapshot)")
     a = p.parse_args()
     if a.node_limit <= 0:
@@ -61,12 +62,12 @@ def main():
     sha = _lib.library_sha16(_lib.LIB_PATH)
     for depth in sorted(a.depths):
         base_nodes = None
-        for split in sorted(a.splits):
+        for split, order in [(s, o) for s in sorted(a.splits) for o in a.order]:
             if split == 0 and depth > _lib.SEARCH_MAX_DEPTH:
                 continue
             if split and not (split < depth <= split + _lib.SEARCH_MAX_DEPTH):
                 continue
-            kw = dict(node_limit=a.node_limit, want_nodes=True, split=split)
+            kw = dict(node_limit=a.node_limit, want_nodes=True, split=split, order=order)
             if split:
                 kw["nodes_per_position"] = a.nodes_per_position
             ops.search(boards[:a.batch], turn[:a.batch], depth, **kw)  # warm-up
@@ -83,9 +84,9 @@ def main():
                     status[int(s)] = status.get(int(s), 0) + int(c)
                 if time.perf_counter() - t_start > a.budget_s:
                     break
-            if split == 0:
+            if split == 0 and order == 0:
                 base_nodes = (nodes, len(ms))
-            line = {"depth": depth, "split": split, "batch": a.batch, "launches": len(ms), "of": len(launches),
+            line = {"depth": depth, "split": split, "order": order, "batch": a.batch, "launches": len(ms), "of": len(launches),
                     "ms_median": statistics.median(ms), "ms_max": max(ms), "ms_sum": sum(ms), "nodes": nodes,
                     "nodes_vs_split0": (nodes / base_nodes[0] if base_nodes and base_nodes[1] == len(ms)
                                         and base_nodes[0] else None),
