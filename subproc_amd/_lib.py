@@ -14,6 +14,7 @@ SEARCH_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_search.
 PLAY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_play.h")
 TREE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_tree.h")
 ORDER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_order.h")
+SOLVE_TREE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve_tree.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -46,6 +47,10 @@ TREE_NOROOM = 4
 TREE_MIN_NODES = 64
 TREE_DEFAULT_NODES = 32768
 ORDER_MAX = 1             # include/othello_order.h
+SOLVE_TREE_MAX_EMPTIES = 16  # include/othello_solve_tree.h
+SOLVE_TREE_NOROOM = 4
+SOLVE_TREE_MIN_NODES = 64
+SOLVE_TREE_DEFAULT_NODES = 65536
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -129,6 +134,13 @@ ORDER_SIGNATURES = {
     "otho_tree_ordered_grid": (_I, [_I64, _I]),
 }
 
+# the split endgame solver, include/othello_solve_tree.h (its own prefix likewise)
+SOLVE_TREE_SIGNATURES = {
+    "othe_solve": (_I, [_P, _P, _I, _I, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _I64, ctypes.c_int32, _P, _I64, _P]),
+    "othe_scratch_bytes": (_I64, [_I64, ctypes.c_int32]),
+    "othe_solve_grid": (_I, [_I64]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -160,7 +172,7 @@ def load():
     except OSError as e:
         raise OthelloLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES, **PLAY_SIGNATURES,
-                              **TREE_SIGNATURES, **ORDER_SIGNATURES}.items():
+                              **TREE_SIGNATURES, **ORDER_SIGNATURES, **SOLVE_TREE_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

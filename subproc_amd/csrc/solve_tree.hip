@@ -1,0 +1,573 @@
+// solve_tree.hip — the split endgame solver for gfx950: one position's exact
+// alpha-beta tree over the whole device (include/othello_solve_tree.h,
+// DESIGN.md §17).  tree.hip's three launches with the solver's semantics:
+//   1. split_solve_expand, one block per position: builds the top of the tree
+//      in the position's slab round by round (solve_tree_core.hpp) until every
+//      node has at most task_empties empties, children counted by popcounts and
+//      placed by a block scan so that they lie in parent order, backs the final
+//      nodes' values up, lists the tasks and writes their count;
+//   2. split_solve_prefix, one block: the exclusive sum of the task counts;
+//   3. split_solve_tasks: solve.hip's persistent loop (one-wave blocks, frames
+//      [depth][field][lane] in LDS, the refill protocol off the caller's work
+//      word unchanged).  A lane takes a task, derives its window from the state
+//      words of its ancestors, runs oths::advance() until the task ends and
+//      folds the result into the tree; the lane that completes the root emits
+//      the position's answer.
+// With order = 1 the third launch is split_solve_tasks_ordered: the same loop
+// around solve_order_core.hpp's advance_ordered().
+//
+// What one block writes and another reads inside the task launch is the state
+// word of a node and the position's node counter, both touched by agent-scope
+// atomics only; the immutable node fields cross a kernel boundary.  No lane
+// waits for another: every loop is bounded by the tree's height, by the
+// children of one node or by node_limit.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <atomic>
+
+#include "../../include/othello.h"
+#include "../../include/othello_solve.h"
+#include "../../include/othello_solve_tree.h"
+#include "bitboard.hpp"
+#include "solve_order_core.hpp"
+#include "solve_tree_core.hpp"
+
+static_assert(OTHE_MAX_EMPTIES == othe::kMaxEmpties && OTHE_NOROOM == othe::kNoRoom &&
+                  OTHE_MIN_NODES == othe::kMinNodes && OTHS_MAX_EMPTIES == oths::kMaxEmpties,
+              "header and core disagree");
+static_assert(OTHS_SKIPPED == oths::kSkipped && OTHS_SOLVED == oths::kSolved && OTHS_INVALID == oths::kInvalid &&
+                  OTHS_LIMIT == oths::kLimit && OTHS_NO_MOVE == oths::kNoMove && OTH_PASS == oths::kPassMove,
+              "header and core disagree");
+
+namespace {
+
+using othe::Node;
+using othe::u32;
+using othe::u64;
+
+constexpr int kTaskBlock = 64;     // one wave
+constexpr int kRefillMin = 8;      // idle lanes that make a wave refill (solve.hip's measurement)
+constexpr int kExpandBlock = 256;
+// true: a task's window comes from the state words as they are when it starts;
+// false: from the expansion's snapshot
+constexpr bool kShareBounds = true;
+
+struct DeviceRules {
+    static __device__ __forceinline__ u64 moves(u64 P, u64 O) { return oth::moves(P, O); }
+    static __device__ __forceinline__ u64 flips(u32 sq, u64 P, u64 O) { return oth::flips_carry(sq, P, O); }
+    static __device__ __forceinline__ u32 lowest(u64 m) { return (u32)__builtin_ctzll(m); }
+    static __device__ __forceinline__ int count(u64 x) { return __popcll(x); }
+};
+
+struct DeviceAtomics {
+    static __device__ __forceinline__ u64 load(u64* p) {
+        return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    static __device__ __forceinline__ bool cas(u64* p, u64& expected, u64 desired) {
+        return __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // an exchange whose return the lane waits for: the word is in place before
+    // the lane's next atomic is issued
+    static __device__ __forceinline__ void store(u64* p, u64 v) {
+        const u64 old = __hip_atomic_exchange(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("" ::"v"(old) : "memory");
+    }
+};
+
+// frames [depth][field][lane]; `base` already points at the lane's column
+struct LdsStack {
+    u32* base;
+    __device__ __forceinline__ u32* at(int depth) const { return base + depth * (oths::kFields * kTaskBlock); }
+    __device__ __forceinline__ void store(int depth, u64 P, u64 O, u64 M, u32 w) {
+        u32* f = at(depth);
+        f[0 * kTaskBlock] = (u32)P;
+        f[1 * kTaskBlock] = (u32)(P >> 32);
+        f[2 * kTaskBlock] = (u32)O;
+        f[3 * kTaskBlock] = (u32)(O >> 32);
+        f[4 * kTaskBlock] = (u32)M;
+        f[5 * kTaskBlock] = (u32)(M >> 32);
+        f[6 * kTaskBlock] = w;
+    }
+    __device__ __forceinline__ void load(int depth, u64& P, u64& O, u64& M, u32& w) const {
+        const u32* f = at(depth);
+        P = (u64)f[0 * kTaskBlock] | ((u64)f[1 * kTaskBlock] << 32);
+        O = (u64)f[2 * kTaskBlock] | ((u64)f[3 * kTaskBlock] << 32);
+        M = (u64)f[4 * kTaskBlock] | ((u64)f[5 * kTaskBlock] << 32);
+        w = f[6 * kTaskBlock];
+    }
+};
+
+// per position, beside its slab
+struct PosHdr {
+    unsigned long long nodes;  // the expansion's, then + every task's (agent atomics in the task launch)
+    u32 ntasks;
+    u32 pad;
+};
+
+// the caller's scratch, cut up: task prefix [n + 1], headers [n], task lists
+// [n][npp], slabs [n][npp]
+struct Scratch {
+    u64* tbase;
+    PosHdr* hdr;
+    u32* tasks;
+    Node* nodes;
+};
+
+inline int64_t round64(int64_t x) { return (x + 63) & ~(int64_t)63; }
+
+inline int64_t scratch_layout(int64_t n, int64_t npp, void* base, Scratch* s) {
+    char* p = static_cast<char*>(base);
+    int64_t off = 0;
+    if (s) s->tbase = reinterpret_cast<u64*>(p + off);
+    off += round64((n + 1) * 8);
+    if (s) s->hdr = reinterpret_cast<PosHdr*>(p + off);
+    off += round64(n * (int64_t)sizeof(PosHdr));
+    if (s) s->tasks = reinterpret_cast<u32*>(p + off);
+    off += round64(n * npp * 4);
+    if (s) s->nodes = reinterpret_cast<Node*>(p + off);
+    off += n * npp * (int64_t)sizeof(Node);
+    return off;
+}
+
+struct Outputs {
+    int8_t* value;
+    uint8_t* best_move;
+    uint8_t* status;
+    u32* nodes;
+};
+
+__device__ __forceinline__ void emit(const Outputs& o, u64 i, int value, u32 mv, u32 status, u64 nodes) {
+    if (o.value) o.value[i] = (int8_t)value;
+    if (o.best_move) o.best_move[i] = (uint8_t)mv;
+    if (o.status) o.status[i] = (uint8_t)status;
+    if (o.nodes) o.nodes[i] = nodes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)nodes;
+}
+
+// ------------------------------------------------------------------ expansion
+struct ExpandArgs {
+    const u64* boards;
+    const uint8_t* turn;
+    Outputs out;
+    Scratch s;
+    u32 npp;
+    int max_empties;
+    int task_empties;
+};
+
+// inclusive block scan of one value per thread; returns the thread's inclusive
+// sum, `total` the block's.  Ends with the block in step.
+__device__ __forceinline__ u32 block_scan(u32* buf, u32 v, u32& total) {
+    const u32 tid = threadIdx.x;
+    buf[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (u32 d = 1; d < (u32)kExpandBlock; d <<= 1) {
+        const u32 add = tid >= d ? buf[tid - d] : 0u;
+        __syncthreads();
+        buf[tid] += add;
+        __syncthreads();
+    }
+    const u32 incl = buf[tid];
+    total = buf[kExpandBlock - 1];
+    __syncthreads();
+    return incl;
+}
+
+__global__ __launch_bounds__(kExpandBlock) void split_solve_expand(ExpandArgs a) {
+    __shared__ u32 scan[kExpandBlock];
+    __shared__ u32 lvl[othe::kMaxRounds + 2];  // round r's nodes are [lvl[r], lvl[r + 1])
+    __shared__ u32 acc;
+    const u32 tid = threadIdx.x;
+    const u64 pos = blockIdx.x;
+    Node* slab = a.s.nodes + pos * a.npp;
+    u32* tasks = a.s.tasks + pos * a.npp;
+    PosHdr* hdr = a.s.hdr + pos;
+    const ulonglong2 b = reinterpret_cast<const ulonglong2*>(a.boards)[pos];
+    const u32 cls = oths::classify(b.x, b.y, 64 - __popcll(b.x | b.y), a.max_empties);
+    if (cls != oths::kSolved) {  // (uniform over the block)
+        if (tid == 0) {
+            emit(a.out, pos, 0, oths::kNoMove, cls, 0);
+            hdr->nodes = 0;
+            hdr->ntasks = 0;
+        }
+        return;
+    }
+    if (tid == 0) {
+        const bool white = a.turn && a.turn[pos] == OTH_WHITE;
+        othe::make_node<DeviceRules>(slab[0], white ? b.y : b.x, white ? b.x : b.y, -1, oths::kNoMove);
+        lvl[0] = 0;
+        lvl[1] = 1;
+        acc = 0;
+    }
+    __syncthreads();
+    u32 begin = 0, end = 1;
+    int rounds = 0;
+    while (rounds < othe::kMaxRounds) {
+        // a round is made whole or not at all
+        u32 mine = 0;
+        for (u32 i = begin + tid; i < end; i += kExpandBlock)
+            mine += othe::child_count<DeviceRules>(slab[i], a.task_empties);
+        if (mine) atomicAdd(&acc, mine);
+        __syncthreads();
+        const u32 total = acc;
+        __syncthreads();
+        if (tid == 0) acc = 0;
+        if (total == 0 || (u64)end + total > (u64)a.npp) break;
+        u32 running = end;
+        for (u32 tile = begin; tile < end; tile += kExpandBlock) {
+            const u32 i = tile + tid;
+            const u32 c = i < end ? othe::child_count<DeviceRules>(slab[i], a.task_empties) : 0u;
+            u32 tile_total;
+            const u32 incl = block_scan(scan, c, tile_total);
+            if (c) othe::expand<DeviceRules>(slab, i, running + incl - c, c);
+            running += tile_total;
+        }
+        begin = end;
+        end += total;
+        rounds++;
+        if (tid == 0) lvl[rounds + 1] = end;
+        __syncthreads();
+    }
+    __syncthreads();
+    // back the values known now up, deepest round first: final nodes, and nodes
+    // all of whose children are done
+    for (int r = rounds; r >= 1; r--) {
+        const u32 lo = lvl[r], hi = lvl[r + 1];
+        for (u32 i = lo + tid; i < hi; i += kExpandBlock) {
+            const u64 w = DeviceAtomics::load(&slab[i].state);
+            if ((slab[i].flags & othe::kFinal) || (slab[i].nchild && othe::count_of(w) == 0))
+                othe::fold<DeviceAtomics>(slab, (u32)slab[i].parent, othe::best_of(w), 0);
+        }
+        __syncthreads();
+    }
+    for (u32 i = tid; i < end; i += kExpandBlock) slab[i].snap = othe::best_of(DeviceAtomics::load(&slab[i].state));
+    // the tasks, in slab order: the order the sequential search would meet them
+    u32 ntasks = 0, deep = 0;
+    for (u32 tile = 0; tile < end; tile += kExpandBlock) {
+        const u32 i = tile + tid;
+        const u32 t = i < end && othe::is_task(slab[i]) ? 1u : 0u;
+        if (t && slab[i].emp > oths::kMaxEmpties) deep = 1;
+        u32 tile_total;
+        const u32 incl = block_scan(scan, t, tile_total);
+        if (t) tasks[ntasks + incl - 1] = i;
+        ntasks += tile_total;
+    }
+    if (deep) atomicOr(&acc, 1u);
+    __syncthreads();
+    if (tid == 0) {
+        hdr->nodes = end - 1;
+        if (acc) {  // the slab is too small for this position at this task size
+            emit(a.out, pos, 0, oths::kNoMove, othe::kNoRoom, end - 1);
+            ntasks = 0;
+        } else if (ntasks == 0) {  // the game ends inside the expanded plies everywhere
+            int value;
+            u32 mv, st;
+            othe::root_result<DeviceAtomics>(slab, value, mv, st);
+            emit(a.out, pos, value, mv, st, end - 1);
+        }
+        hdr->ntasks = ntasks;
+    }
+}
+
+// ------------------------------------------------------------------ prefix
+__global__ __launch_bounds__(kExpandBlock) void split_solve_prefix(Scratch s, u64 n) {
+    __shared__ u32 scan[kExpandBlock];
+    u64 running = 0;
+    for (u64 tile = 0; tile < n; tile += kExpandBlock) {
+        const u64 i = tile + threadIdx.x;
+        const u32 c = i < n ? s.hdr[i].ntasks : 0u;
+        u32 tile_total;
+        const u32 incl = block_scan(scan, c, tile_total);
+        if (i < n) s.tbase[i] = running + incl - c;
+        running += tile_total;
+    }
+    if (threadIdx.x == 0) s.tbase[n] = running;
+}
+
+// ------------------------------------------------------------------ tasks
+struct TaskArgs {
+    Outputs out;
+    Scratch s;
+    unsigned long long* work;
+    u64 n;
+    u64 lanes;  // of the grid: with the task count, what the launch's requests add up to
+    u32 npp;
+    u32 limit;
+};
+
+// (split_solve_tasks_ordered below is this loop again with the ordered machine: a change here belongs there too)
+__global__ __launch_bounds__(kTaskBlock) void split_solve_tasks(TaskArgs a) {
+    __shared__ u32 frames[oths::kFrames * oths::kFields * kTaskBlock];
+    const u32 lane = threadIdx.x;
+    const u64 ntasks = a.s.tbase[a.n];
+    const u64 total = ntasks + a.lanes;
+    LdsStack stk{frames + lane};
+    oths::Lane L;
+    L.depth = -1;
+    u64 pos = 0;
+    u32 node = 0;
+    bool exhausted = false;  // the lane has made its failing request
+    for (;;) {
+        const bool idle = L.depth < 0;
+        const bool want = idle && !exhausted;
+        const u64 wantm = __ballot(want);
+        const u64 busym = __ballot(!idle);
+        if ((wantm | busym) == 0) break;
+        const u64 cnt = (u64)__popcll(wantm);
+        bool done = false;  // the lane's task ended in this turn of the loop
+        int v = 0;
+        u64 lim = 0;
+        u32 spent = 0;
+        if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
+            u64 base = 0;
+            if (lane == 0) {
+                base = atomicAdd(a.work, cnt);
+                if (base + cnt == total) atomicExch(a.work, 0ull);  // every request is made: reset
+            }
+            base = __shfl(base, 0);
+            if (want) {
+                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
+                if (g >= ntasks) {
+                    exhausted = true;
+                } else {
+                    u64 lo = 0, hi = a.n;  // the last position whose first task is <= g
+                    while (hi - lo > 1) {
+                        const u64 mid = (lo + hi) >> 1;
+                        if (a.s.tbase[mid] <= g) lo = mid; else hi = mid;
+                    }
+                    pos = lo;
+                    node = a.s.tasks[pos * a.npp + (g - a.s.tbase[pos])];
+                    Node* slab = a.s.nodes + pos * a.npp;
+                    int alpha, beta;
+                    othe::window<DeviceAtomics>(slab, node, kShareBounds, alpha, beta);
+                    if (alpha >= beta) {  // cut off before it began: it reports its beta
+                        done = true;
+                        v = beta;
+                    } else {
+                        othe::start_task(L, slab[node], alpha, beta);
+                    }
+                }
+            }
+        }
+        if (L.depth >= 0) {
+            oths::advance<DeviceRules>(L, stk, a.limit);
+            if (L.depth < 0) {
+                done = true;
+                v = L.value;
+                lim = L.status == oths::kLimit ? othe::kLimitBit : 0ull;
+                spent = L.nodes;
+            }
+        }
+        if (done) {
+            Node* slab = a.s.nodes + pos * a.npp;
+            PosHdr* hdr = a.s.hdr + pos;
+            const u64 before = __hip_atomic_fetch_add(&hdr->nodes, (unsigned long long)spent, __ATOMIC_RELAXED,
+                                                      __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("" ::"v"(before) : "memory");
+            if (othe::fold_up<DeviceAtomics>(slab, node, v, lim)) {
+                int value;
+                u32 mv, st;
+                othe::root_result<DeviceAtomics>(slab, value, mv, st);
+                emit(a.out, pos, value, mv, st,
+                     __hip_atomic_load(&hdr->nodes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            }
+        }
+    }
+}
+
+// split_solve_tasks with solve_order_core.hpp's machine inside a task (order =
+// 1): the same loop, the scoring state Q beside the lane's L.  Kept as a kernel
+// of its own text, as tree.hip's pair is.
+__global__ __launch_bounds__(kTaskBlock) void split_solve_tasks_ordered(TaskArgs a) {
+    __shared__ u32 frames[oths::kFrames * oths::kFields * kTaskBlock];
+    const u32 lane = threadIdx.x;
+    const u64 ntasks = a.s.tbase[a.n];
+    const u64 total = ntasks + a.lanes;
+    LdsStack stk{frames + lane};
+    oths::Lane L;
+    L.depth = -1;
+    othm::Order Q;
+    othm::order_reset(Q);
+    u64 pos = 0;
+    u32 node = 0;
+    bool exhausted = false;  // the lane has made its failing request
+    for (;;) {
+        const bool idle = L.depth < 0;
+        const bool want = idle && !exhausted;
+        const u64 wantm = __ballot(want);
+        const u64 busym = __ballot(!idle);
+        if ((wantm | busym) == 0) break;
+        const u64 cnt = (u64)__popcll(wantm);
+        bool done = false;  // the lane's task ended in this turn of the loop
+        int v = 0;
+        u64 lim = 0;
+        u32 spent = 0;
+        if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
+            u64 base = 0;
+            if (lane == 0) {
+                base = atomicAdd(a.work, cnt);
+                if (base + cnt == total) atomicExch(a.work, 0ull);  // every request is made: reset
+            }
+            base = __shfl(base, 0);
+            if (want) {
+                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
+                if (g >= ntasks) {
+                    exhausted = true;
+                } else {
+                    u64 lo = 0, hi = a.n;  // the last position whose first task is <= g
+                    while (hi - lo > 1) {
+                        const u64 mid = (lo + hi) >> 1;
+                        if (a.s.tbase[mid] <= g) lo = mid; else hi = mid;
+                    }
+                    pos = lo;
+                    node = a.s.tasks[pos * a.npp + (g - a.s.tbase[pos])];
+                    Node* slab = a.s.nodes + pos * a.npp;
+                    int alpha, beta;
+                    othe::window<DeviceAtomics>(slab, node, kShareBounds, alpha, beta);
+                    if (alpha >= beta) {  // cut off before it began: it reports its beta
+                        done = true;
+                        v = beta;
+                    } else {
+                        othe::start_task(L, slab[node], alpha, beta);
+                        othm::order_reset(Q);
+                    }
+                }
+            }
+        }
+        if (L.depth >= 0) {
+            oths::advance_ordered<DeviceRules>(L, Q, stk, a.limit);
+            if (L.depth < 0) {
+                done = true;
+                v = L.value;
+                lim = L.status == oths::kLimit ? othe::kLimitBit : 0ull;
+                spent = L.nodes;
+            }
+        }
+        if (done) {
+            Node* slab = a.s.nodes + pos * a.npp;
+            PosHdr* hdr = a.s.hdr + pos;
+            const u64 before = __hip_atomic_fetch_add(&hdr->nodes, (unsigned long long)spent, __ATOMIC_RELAXED,
+                                                      __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("" ::"v"(before) : "memory");
+            if (othe::fold_up<DeviceAtomics>(slab, node, v, lim)) {
+                int value;
+                u32 mv, st;
+                othe::root_result<DeviceAtomics>(slab, value, mv, st);
+                emit(a.out, pos, value, mv, st,
+                     __hip_atomic_load(&hdr->nodes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            }
+        }
+    }
+}
+
+inline int status_of(hipError_t e) { return e == hipSuccess ? OTH_OK : -(int)e; }
+
+int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v && *v ? atoi(v) : dflt;
+}
+
+// blocks of the task kernel (order 0) or the ordered one (1) a device holds at
+// once, resolved on first use
+constexpr int kMaxDevices = 64;
+std::atomic<int> g_resident[2][kMaxDevices];
+
+int resident_blocks(int order) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= kMaxDevices) return -1;
+    int r = g_resident[order][dev].load(std::memory_order_acquire);
+    if (r > 0) return r;
+    int cus = 256, per_cu = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const void* kernel = order ? reinterpret_cast<const void*>(split_solve_tasks_ordered)
+                               : reinterpret_cast<const void*>(split_solve_tasks);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kTaskBlock, 0);
+    (void)hipGetLastError();
+    r = std::max(cus, 1) * (per_cu > 0 ? per_cu : 4);
+    g_resident[order][dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
+    return r;
+}
+
+int task_grid(int64_t tasks, int order) {
+    const int resident = resident_blocks(order);
+    if (resident <= 0) return -1;
+    const int cap = std::min(std::max(env_int("OTH_SOLVE_BLOCKS", resident), 1), resident);
+    return (int)std::min<int64_t>(std::max<int64_t>((tasks + kTaskBlock - 1) / kTaskBlock, 1), (int64_t)cap);
+}
+
+// n * npp, or -1 when the scratch would not fit 2^62 bytes
+int64_t slab_nodes(int64_t n, int64_t npp) {
+    if (n < 0 || npp < OTHE_MIN_NODES || npp > (1 << 30)) return -1;
+    if (n > 0 && npp > ((int64_t)1 << 55) / n) return -1;
+    return n * npp;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t othe_scratch_bytes(int64_t n, int32_t nodes_per_position) {
+    if (slab_nodes(n, nodes_per_position) < 0) return OTH_EINVAL;
+    return scratch_layout(n, nodes_per_position, nullptr, nullptr);
+}
+
+int othe_solve(const uint64_t* boards, const uint8_t* turn, int max_empties, int task_empties, int order,
+               uint32_t node_limit, int8_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes,
+               void* scratch, int64_t scratch_bytes, int32_t nodes_per_position, uint64_t* work, int64_t n,
+               void* stream) {
+    if (order < 0 || order > 1) return OTH_EINVAL;
+    if (n < 0 || n > 0x7FFFFFFF || !work || (n > 0 && !boards)) return OTH_EINVAL;
+    if (max_empties < 0 || max_empties > OTHE_MAX_EMPTIES || task_empties < 1 || task_empties > OTHS_MAX_EMPTIES)
+        return OTH_EINVAL;
+    const int64_t total_nodes = slab_nodes(n, nodes_per_position);
+    if (total_nodes < 0) return OTH_EINVAL;
+    if (n == 0) return OTH_OK;
+    if (!scratch || ((uintptr_t)scratch & 7) || scratch_bytes < scratch_layout(n, nodes_per_position, nullptr, nullptr))
+        return OTH_EINVAL;
+    // a position has no more tasks than its slab holds
+    const int grid = task_grid(total_nodes, order);
+    if (grid <= 0) return status_of(hipErrorInvalidDevice);
+    hipStream_t st = (hipStream_t)stream;
+    Outputs out{value, best_move, status, nodes};
+    ExpandArgs e;
+    e.boards = boards;
+    e.turn = turn;
+    e.out = out;
+    scratch_layout(n, nodes_per_position, scratch, &e.s);
+    e.npp = (u32)nodes_per_position;
+    e.max_empties = max_empties;
+    e.task_empties = task_empties;
+    split_solve_expand<<<(unsigned)n, kExpandBlock, 0, st>>>(e);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return status_of(err);
+    split_solve_prefix<<<1, kExpandBlock, 0, st>>>(e.s, (u64)n);
+    err = hipGetLastError();
+    if (err != hipSuccess) return status_of(err);
+    TaskArgs t;
+    t.out = out;
+    t.s = e.s;
+    t.work = reinterpret_cast<unsigned long long*>(work);
+    t.n = (u64)n;
+    t.lanes = (u64)grid * kTaskBlock;
+    t.npp = (u32)nodes_per_position;
+    t.limit = node_limit ? node_limit : OTHS_DEFAULT_NODE_LIMIT;
+    if (order)
+        split_solve_tasks_ordered<<<(unsigned)grid, kTaskBlock, 0, st>>>(t);
+    else
+        split_solve_tasks<<<(unsigned)grid, kTaskBlock, 0, st>>>(t);
+    return status_of(hipGetLastError());
+}
+
+int othe_solve_grid(int64_t tasks) {
+    if (tasks < 0) return OTH_EINVAL;
+    if (tasks == 0) return 0;
+    const int grid = task_grid(tasks, 0);
+    return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
+}
+
+}  // extern "C"

@@ -31,7 +31,10 @@ policy).  ``--params FILE`` loads the table from the file paramgen.py writes
 ``--solve-empties K`` (K = 1..12) plays the endgame perfectly, as the engines
 this one stands in for do: with at most K empty squares and a legal move, the
 move is the exact solver's (ops.solve: best final disc difference, ties to the
-lowest square), whatever the policy.
+lowest square), whatever the policy.  ``--solve-task-empties T`` (T = 1..12)
+makes that solve the split solver (ops.solve(task_empties=T), the position's
+tree spread over the whole device) and lets K go to 16; ``--solve-order 1``
+orders the moves inside its tasks (default: ``--order``'s value).
 ``--policy search --depth D`` (D = 1..8) looks D plies ahead: the move is
 ops.search's, a fixed-depth alpha-beta with the eval table at the horizon (one
 launch per ``go``; depth 1 is the "eval" policy's move).  ``--solve-empties``
@@ -54,9 +57,17 @@ from .codec import handstr_from_coord
 
 
 class Engine:
-    def __init__(self, name="GPU", policy="greedy", seed=0, weights=None, solve_empties=0, depth=1, split=0, order=0):
-        if not 0 <= solve_empties <= _lib.SOLVE_MAX_EMPTIES:
-            raise ValueError(f"solve_empties must lie in 0..{_lib.SOLVE_MAX_EMPTIES}")
+    def __init__(self, name="GPU", policy="greedy", seed=0, weights=None, solve_empties=0, depth=1, split=0, order=0,
+                 solve_task_empties=None, solve_order=None):
+        top = _lib.SOLVE_MAX_EMPTIES if solve_task_empties is None else _lib.SOLVE_TREE_MAX_EMPTIES
+        if not 0 <= solve_empties <= top:
+            raise ValueError(f"solve_empties must lie in 0..{top}" + (
+                "" if solve_task_empties is not None else
+                f" (up to {_lib.SOLVE_TREE_MAX_EMPTIES} with solve_task_empties)"))
+        if solve_task_empties is not None and not 1 <= solve_task_empties <= _lib.SOLVE_MAX_EMPTIES:
+            raise ValueError(f"solve_task_empties must lie in 1..{_lib.SOLVE_MAX_EMPTIES}")
+        if solve_order is not None and solve_order not in (0, 1):
+            raise ValueError("solve_order must be 0 or 1")
         if not 0 <= split <= _lib.TREE_MAX_SPLIT:
             raise ValueError(f"split must lie in 0..{_lib.TREE_MAX_SPLIT}")
         if not 1 <= depth <= _lib.SEARCH_MAX_DEPTH + split:
@@ -64,6 +75,9 @@ class Engine:
         if not 0 <= order <= _lib.ORDER_MAX:
             raise ValueError(f"order must lie in 0..{_lib.ORDER_MAX}")
         self.solve_empties = solve_empties
+        self.solve_task_empties = solve_task_empties
+        # (the solver's tasks take the search's --order unless --solve-order says otherwise)
+        self.solve_order = (order if solve_order is None else solve_order) if solve_task_empties is not None else 0
         self.order = order
         self.depth = depth
         # (a depth the split leaves no plies below is searched unsplit)
@@ -103,8 +117,9 @@ class Engine:
         return handstr_from_coord(*puts[k])
 
     def _choose_solved(self):
-        """The solver's move for the side to move (one oths_solve launch), or
-        None when it gives none (more than solve_empties empties)."""
+        """The solver's move for the side to move (one oths_solve launch, or
+        othe_solve's with solve_task_empties), or None when it gives none (more
+        than solve_empties empties; a node limit; a tree that did not fit)."""
         b = self.board
         bl, wh = b.bitboards()
         if 64 - bin(bl | wh).count("1") > self.solve_empties:
@@ -114,7 +129,8 @@ class Engine:
         side = torch.full((1,), b.turn, dtype=torch.uint8, device=dev)
         # (a position that would need more than 2**24 nodes -- none at <= 12
         # empties in DESIGN.md §12's samples -- falls back to the policy)
-        r = ops.solve(boards, side, max_empties=self.solve_empties, node_limit=1 << 24)
+        r = ops.solve(boards, side, max_empties=self.solve_empties, node_limit=1 << 24,
+                      task_empties=self.solve_task_empties, order=self.solve_order)
         sq = int(r.best_move.cpu()[0])
         if int(r.status.cpu()[0]) != _lib.SOLVE_SOLVED or sq > 63:
             return None
@@ -175,6 +191,9 @@ class Engine:
                     " order=%d" % self.order if self.order > 0 else "") + extra
             if self.solve_empties > 0:
                 extra += " solve_empties=%d" % self.solve_empties
+                if self.solve_task_empties is not None:
+                    extra += " solve_task_empties=%d" % self.solve_task_empties + (
+                        " solve_order=%d" % self.solve_order if self.solve_order > 0 else "")
             out("%s policy=%s%s" % (self.name, self.policy, extra))
         elif cmd == "verbose 1":
             b = self.board
@@ -216,10 +235,16 @@ def main(argv=None):
     p.add_argument("--order", type=int, choices=[0, 1], default=0,
                    help="policy search's move ordering: 0 lowest square first, 1 ordered (same moves, smaller tree)")
     p.add_argument("--solve-empties", type=int, default=0, metavar="K",
-                   help="play the exact solver's move once at most K squares are empty (0 = never, max 12)")
+                   help="play the exact solver's move once at most K squares are empty (0 = never, max 12; "
+                        "max 16 with --solve-task-empties)")
+    p.add_argument("--solve-task-empties", type=int, default=None, metavar="T",
+                   help="spread the exact solver's tree over the device: nodes of at most T empties become tasks (1..12)")
+    p.add_argument("--solve-order", type=int, choices=[0, 1], default=None,
+                   help="move ordering inside the split solver's tasks (default: --order's value)")
     a = p.parse_args(argv)
     weights = params.read_paramgen(a.params)[1] if a.params else None
-    eng = Engine(a.name, a.policy, a.seed, weights, a.solve_empties, a.depth, a.split, a.order)
+    eng = Engine(a.name, a.policy, a.seed, weights, a.solve_empties, a.depth, a.split, a.order,
+                 a.solve_task_empties, a.solve_order)
 
     def out(s):
         sys.stdout.write(s + "\n")

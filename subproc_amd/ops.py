@@ -413,7 +413,8 @@ def rollout_runner(n, seed, game_id0=0, policy="eval", weights_a=None, weights_b
 SolveResult = namedtuple("SolveResult", "value best_move status nodes")
 
 
-def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=None):
+def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=None, task_empties=None, order=0,
+          nodes_per_position=_lib.SOLVE_TREE_DEFAULT_NODES):
     """Exact endgame solve (oths_solve, include/othello_solve.h): for every
     position with at most ``max_empties`` (0..12) empty squares, the final disc
     difference under perfect play by both sides, from the mover's side (White
@@ -430,6 +431,24 @@ def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=Non
 
     ``work`` as in :func:`rollout`: default the current stream's
     :func:`work_word` (shared with the rollouts), required under graph capture.
+
+    ``task_empties`` = T (1..12) is the split solver (othe_solve,
+    include/othello_solve_tree.h): the top of every position's tree is
+    expanded, down to nodes of at most T empties, into a tree of at most
+    ``nodes_per_position`` nodes in device memory, and the nodes at its bottom
+    are solved by all the device's lanes, sharing bounds.  Values, moves and
+    statuses are the same; ``max_empties`` may go to 16; ``node_limit`` bounds
+    each task; a position whose tree does not fit its slab far enough down (a
+    task would have more than 12 empties) ends as _lib.SOLVE_TREE_NOROOM (value
+    0, move 255); ``nodes`` then depends on timing.  ``order`` = 1 orders the
+    moves inside the tasks (the same results from a smaller tree; only a
+    position within reach of ``node_limit`` may end differently).  It pays for
+    small batches, down to one position.  The default slab, 65,536 nodes
+    (3.25 MiB per position), holds four full plies of every 16-empties root of
+    tests/golden/solve_deep/solve_deep.npz and of tools/solve_tree_bench.py's set, so
+    none of them ends as NOROOM.  The scratch (othe_scratch_bytes) is allocated
+    here, so this form does not run under graph capture.  Without
+    ``task_empties`` the call is oths_solve's, and ``order`` must be 0.
     """
     n = _n(boards)
     capturing = torch.cuda.is_current_stream_capturing()
@@ -438,6 +457,11 @@ def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=Non
                            "tensor zeroed before the capture, one per captured launch")
     if not 0 <= int(node_limit) < 2**32:
         raise ValueError("node_limit must fit 32 bits")
+    if task_empties is not None:
+        return _solve_split(boards, turn, n, int(max_empties), int(task_empties), int(order), int(node_limit),
+                            want_nodes, work, int(nodes_per_position), capturing)
+    if int(order) != 0:
+        raise ValueError("ops.solve orders moves only inside the split solver's tasks: order needs task_empties")
     d = boards.device
     pb = _dev(boards, "boards", torch.int64)
     pt = _dev(turn, "turn", torch.uint8, (n,), d)
@@ -456,6 +480,41 @@ def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=Non
             elif not capturing:
                 w.zero_()
         check(rc, "oths_solve")
+    return SolveResult(val, mv, st, nd)
+
+
+def _solve_split(boards, turn, n, max_empties, task_empties, order, node_limit, want_nodes, work, nodes_per_position,
+                 capturing):
+    """:func:`solve` with task_empties set: othe_solve on a scratch of its own."""
+    if capturing:
+        raise RuntimeError("ops.solve(task_empties=...) allocates its scratch and does not run under graph capture")
+    if not -2**31 <= nodes_per_position < 2**31:
+        raise ValueError("nodes_per_position must fit 32 bits")
+    d = boards.device
+    pb = _dev(boards, "boards", torch.int64)
+    pt = _dev(turn, "turn", torch.uint8, (n,), d)
+    lib = _lib.load()
+    size = lib.othe_scratch_bytes(n, nodes_per_position)
+    if size < 0:
+        check(int(size), "othe_scratch_bytes")
+    val = torch.empty(n, dtype=torch.int8, device=d)
+    mv = torch.empty(n, dtype=torch.uint8, device=d)
+    st = torch.empty(n, dtype=torch.uint8, device=d)
+    nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
+    scratch = torch.empty(max(int(size), 8) // 8, dtype=torch.int64, device=d)
+    w = work_word(d) if work is None else work
+    pw = _dev(w, "work", torch.int64, (1,), d)
+    with torch.cuda.device(d):
+        rc = lib.othe_solve(pb, pt, max_empties, task_empties, order, node_limit, val.data_ptr(), mv.data_ptr(),
+                            st.data_ptr(), None if nd is None else nd.data_ptr(), scratch.data_ptr(),
+                            scratch.numel() * 8, nodes_per_position, pw, n, _stream())
+        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
+            if work is None:
+                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
+            else:
+                w.zero_()
+        check(rc, "othe_solve")
+    # (the caching allocator hands the scratch to later work of THIS stream only)
     return SolveResult(val, mv, st, nd)
 
 

@@ -1,0 +1,105 @@
+#!/usr/bin/env python
+"""Latency of the split solver (ops.solve(task_empties=T, order=o)) against the
+one-lane solver (ops.solve) and the split search at full depth
+(ops.search(depth=E, split=4, order=1)) in the same process, by empties.
+
+Positions: the first --positions of tests/solve_cases.ladder(E, 64) for each E
+of --empties, --batch per launch.  One JSON line per (E, method): median and
+worst wall time of a launch (host clock around the call and a synchronise,
+after one warm-up launch per method on the first position), the nodes of all
+launches (under a split they depend on timing), the statuses, library_sha16.
+Methods: "lane" (E <= 12), "search" (E <= 12), "T<t>o<o>" for every t of
+--task-empties and o of --order.  Every launch carries --node-limit (per
+position for "lane", per task otherwise); a method stops early once it has used
+--budget-s seconds and says how many launches it timed.  Nothing raises a
+limit silently: a position that ends as LIMIT or NOROOM is counted in
+status_counts and named in "unsolved".
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from subproc_amd import _lib  # noqa: E402
+
+
+def main():
+    p = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    p.add_argument("--empties", type=int, nargs="+", default=[10, 12, 14, 16])
+    p.add_argument("--task-empties", type=int, nargs="+", default=[8, 10, 12])
+    p.add_argument("--order", type=int, nargs="+", choices=[0, 1], default=[0, 1])
+    p.add_argument("--methods", nargs="+", default=["lane", "search", "split"])
+    p.add_argument("--positions", type=int, default=64)
+    p.add_argument("--batch", type=int, default=1)
+    p.add_argument("--node-limit", type=int, default=1 << 26)
+    p.add_argument("--nodes-per-position", type=int, default=_lib.SOLVE_TREE_DEFAULT_NODES)
+    p.add_argument("--budget-s", type=float, default=20.0)
+    p.add_argument("--tag", default="", help="recorded on every line")
+    p.add_argument("--lib", default=None, help="another build of the library (the parent commit's, for lane and search)")
+    a = p.parse_args()
+    if a.node_limit <= 0:
+        p.error("every launch carries a node limit")
+    if a.lib:
+        _lib.LIB_PATH = os.path.abspath(a.lib)
+        _lib.SOLVE_TREE_SIGNATURES = {}  # (a build from before this set has nothing to bind it to)
+        if "split" in a.methods:
+            p.error("--lib measures the methods the other build has: --methods lane search")
+    import solve_cases
+    from subproc_amd import ops
+
+    sha = _lib.library_sha16(_lib.LIB_PATH)
+    for e in sorted(a.empties):
+        b, t = solve_cases.ladder(e, 64)
+        k = min(a.positions, len(t))
+        boards = ops.from_numpy_u64(np.array(b[:k]), "cuda")
+        turn = torch.from_numpy(np.array(t[:k])).cuda()
+        methods = []
+        if "lane" in a.methods and e <= _lib.SOLVE_MAX_EMPTIES:
+            methods.append(("lane", lambda bb, tt: ops.solve(bb, tt, max_empties=e, node_limit=a.node_limit,
+                                                             want_nodes=True)))
+        if "search" in a.methods and 4 < e <= _lib.SEARCH_MAX_DEPTH + 4:
+            methods.append(("search", lambda bb, tt: ops.search(bb, tt, e, node_limit=a.node_limit, want_nodes=True,
+                                                                split=4, order=1)))
+        if "split" in a.methods:
+            for te in a.task_empties:
+                for o in a.order:
+                    methods.append(("T%do%d" % (te, o), lambda bb, tt, te=te, o=o: ops.solve(
+                        bb, tt, max_empties=e, node_limit=a.node_limit, want_nodes=True, task_empties=te, order=o,
+                        nodes_per_position=a.nodes_per_position)))
+        launches = [(i, i + a.batch) for i in range(0, k - a.batch + 1, a.batch)]
+        for name, fn in methods:
+            fn(boards[:1], turn[:1])  # warm-up
+            torch.cuda.synchronize()
+            ms, nodes, status, unsolved = [], 0, {}, []
+            t_start = time.perf_counter()
+            for lo, hi in launches:
+                t0 = time.perf_counter()
+                r = fn(boards[lo:hi], turn[lo:hi])
+                torch.cuda.synchronize()
+                ms.append((time.perf_counter() - t0) * 1e3)
+                nodes += int(r.nodes.cpu().numpy().view(np.uint32).astype(np.int64).sum())
+                st = r.status.cpu().numpy()
+                for s, c in zip(*np.unique(st, return_counts=True)):
+                    status[int(s)] = status.get(int(s), 0) + int(c)
+                unsolved += [lo + int(i) for i in np.nonzero(st != 1)[0]]
+                if time.perf_counter() - t_start > a.budget_s:
+                    break
+            line = {"empties": e, "method": name, "batch": a.batch, "launches": len(ms), "of": len(launches),
+                    "ms_median": statistics.median(ms), "ms_max": max(ms), "ms_sum": sum(ms), "nodes": nodes,
+                    "status_counts": status, "unsolved": unsolved, "node_limit": a.node_limit,
+                    "nodes_per_position": a.nodes_per_position if name.startswith("T") else None,
+                    "solve_blocks": os.environ.get("OTH_SOLVE_BLOCKS"), "tag": a.tag, "library_sha16": sha}
+            print(json.dumps(line), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
