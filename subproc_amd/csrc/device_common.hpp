@@ -1,0 +1,142 @@
+// device_common.hpp — what the search files (solve.hip, search.hip, play.hip,
+// tree.hip, solve_tree.hip) give their state machines on the device, and the
+// host-side plumbing of their launches, stated once.
+//   * DeviceRules: the rules parameter R of the cores, bitboard.hpp's moves()
+//     and flips_carry(), the ones the step kernel plays by;
+//   * DeviceAtomics: the atomics parameter A of the split trees' state words;
+//   * LdsStack9 / LdsStack7: the stack parameter S, frames in LDS indexed
+//     [depth][field][lane] in 32-bit words, so a wave's access is one word per
+//     bank whatever depth each lane is at.  9 words: search_core.hpp's frame,
+//     7: solve_core.hpp's;
+//   * kRefillMin, status_of(), env_int(), ResidentBlocks.
+// Everything device-side is force-inlined: no kernel gets a symbol from here.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <atomic>
+
+#include "../../include/othello.h"
+#include "bitboard.hpp"
+
+namespace othd {
+
+typedef uint64_t u64;
+typedef uint32_t u32;
+
+// idle lanes that make a wave refill from the work word.  Measured with the
+// solver (solve.hip's header); the other kernels take it over.
+constexpr int kRefillMin = 8;
+
+struct DeviceRules {
+    static __device__ __forceinline__ u64 moves(u64 P, u64 O) { return oth::moves(P, O); }
+    static __device__ __forceinline__ u64 flips(u32 sq, u64 P, u64 O) { return oth::flips_carry(sq, P, O); }
+    static __device__ __forceinline__ u32 lowest(u64 m) { return (u32)__builtin_ctzll(m); }
+    static __device__ __forceinline__ int count(u64 x) { return __popcll(x); }
+    // int8 weight x count <= 64: exact in 24 bits, a full-rate multiply
+    static __device__ __forceinline__ int mul(int w, int c) { return __mul24(w, c); }
+};
+
+struct DeviceAtomics {
+    static __device__ __forceinline__ u64 load(u64* p) {
+        return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    static __device__ __forceinline__ bool cas(u64* p, u64& expected, u64 desired) {
+        return __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                    __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // an exchange whose return the lane waits for: the word is in place before
+    // the lane's next atomic is issued
+    static __device__ __forceinline__ void store(u64* p, u64 v) {
+        const u64 old = __hip_atomic_exchange(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("" ::"v"(old) : "memory");
+    }
+};
+
+// the search's frames in a block of kBlock lanes; `base` already points at the
+// lane's column
+template <int kBlock>
+struct LdsStack9 {
+    static constexpr int kFields = 9;
+    u32* base;
+    __device__ __forceinline__ u32* at(int depth) const { return base + depth * (kFields * kBlock); }
+    __device__ __forceinline__ void store(int depth, u64 P, u64 O, u64 M, int alpha, int beta, u32 w) {
+        u32* f = at(depth);
+        f[0 * kBlock] = (u32)P;
+        f[1 * kBlock] = (u32)(P >> 32);
+        f[2 * kBlock] = (u32)O;
+        f[3 * kBlock] = (u32)(O >> 32);
+        f[4 * kBlock] = (u32)M;
+        f[5 * kBlock] = (u32)(M >> 32);
+        f[6 * kBlock] = (u32)alpha;
+        f[7 * kBlock] = (u32)beta;
+        f[8 * kBlock] = w;
+    }
+    __device__ __forceinline__ void load(int depth, u64& P, u64& O, u64& M, int& alpha, int& beta, u32& w) const {
+        const u32* f = at(depth);
+        P = (u64)f[0 * kBlock] | ((u64)f[1 * kBlock] << 32);
+        O = (u64)f[2 * kBlock] | ((u64)f[3 * kBlock] << 32);
+        M = (u64)f[4 * kBlock] | ((u64)f[5 * kBlock] << 32);
+        alpha = (int)f[6 * kBlock];
+        beta = (int)f[7 * kBlock];
+        w = f[8 * kBlock];
+    }
+};
+
+// the solver's frames: the window and the flags share the seventh word
+template <int kBlock>
+struct LdsStack7 {
+    static constexpr int kFields = 7;
+    u32* base;
+    __device__ __forceinline__ u32* at(int depth) const { return base + depth * (kFields * kBlock); }
+    __device__ __forceinline__ void store(int depth, u64 P, u64 O, u64 M, u32 w) {
+        u32* f = at(depth);
+        f[0 * kBlock] = (u32)P;
+        f[1 * kBlock] = (u32)(P >> 32);
+        f[2 * kBlock] = (u32)O;
+        f[3 * kBlock] = (u32)(O >> 32);
+        f[4 * kBlock] = (u32)M;
+        f[5 * kBlock] = (u32)(M >> 32);
+        f[6 * kBlock] = w;
+    }
+    __device__ __forceinline__ void load(int depth, u64& P, u64& O, u64& M, u32& w) const {
+        const u32* f = at(depth);
+        P = (u64)f[0 * kBlock] | ((u64)f[1 * kBlock] << 32);
+        O = (u64)f[2 * kBlock] | ((u64)f[3 * kBlock] << 32);
+        M = (u64)f[4 * kBlock] | ((u64)f[5 * kBlock] << 32);
+        w = f[6 * kBlock];
+    }
+};
+
+inline int status_of(hipError_t e) { return e == hipSuccess ? OTH_OK : -(int)e; }
+
+inline int env_int(const char* name, int dflt) {
+    const char* v = getenv(name);
+    return v && *v ? atoi(v) : dflt;
+}
+
+// blocks of one kernel a device holds at once, resolved on first use.  One
+// object (static storage: zeroes) per kernel.
+constexpr int kMaxDevices = 64;
+struct ResidentBlocks {
+    std::atomic<int> cached[kMaxDevices];
+    // < 0: the current device is out of range
+    int get(const void* kernel, int block) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (dev < 0 || dev >= kMaxDevices) return -1;
+        int r = cached[dev].load(std::memory_order_acquire);
+        if (r > 0) return r;
+        int cus = 256, per_cu = 0;
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, 0);
+        (void)hipGetLastError();
+        r = std::max(cus, 1) * (per_cu > 0 ? per_cu : 4);
+        cached[dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
+        return r;
+    }
+};
+
+}  // namespace othd

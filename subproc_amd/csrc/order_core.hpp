@@ -1,7 +1,10 @@
 // order_core.hpp — search_core.hpp's state machine with MOVE ORDERING: the same
-// frames, Lane, start(), pop() and eval(), a different choice of the next move.
-// Written once for the device (search.hip, play.hip, tree.hip: the *_ordered
-// kernels) and the host (tools/diag/*_host.cpp with order = 1).  DESIGN.md §16.
+// frames, Lane, start(), pop(), settle_child() and eval(), a different choice of
+// the next move.  Written once for the device (search.hip, play.hip, tree.hip:
+// the *_ordered kernels) and the host (tools/diag/*_host.cpp with order = 1).
+// The choice itself (the Order state and its pieces below) is the solver's too:
+// solve_order_core.hpp puts it in front of solve_core.hpp's transitions.
+// DESIGN.md §16.
 //
 // THE RULE (the contract of `order = 1`).  A frame with moves left picks:
 //   1. SINGLE MOVE.  One move left: it is played.
@@ -84,41 +87,52 @@ OTHM_FN u32 static_pick(u64 m) {
     return R::lowest(c);
 }
 
-// a finished ROOT child's value with the root tie rule; other frames: apply_score
-template <bool kRootTie>
-OTHM_FN void apply_score_ordered(Lane& L, int score) {
-    if (kRootTie && L.depth == 0 && score == L.alpha && L.root_mv < L.best_mv && L.best_mv < 64u)
-        L.best_mv = L.root_mv;  // (the move was searched from alpha - 1: the score is exact)
-    apply_score(L, score);
+// THE HEAD, shared with the solver's ordered machine (solve_order_core.hpp),
+// in three pieces.  A step with moves left calls order_begin(); then Q.cand != 0
+// says that it SCORES: it places order_candidate()'s square and hands the
+// child's moves to order_score(); otherwise it PLAYS order_choice()'s square.
+
+// begin a pick where rule 2 applies: `mobile()` is its size test, asked only of
+// a frame with >= 2 moves left and no pick under way
+template <class Mobile>
+OTHM_FN void order_begin(Order& Q, u64 M, Mobile mobile) {
+    if (Q.cand == 0 && Q.pick >= 64u && (M & (M - 1)) != 0 && mobile()) {
+        Q.cand = M;  // this step scores its first candidate
+        Q.pick = ~0u;
+    }
 }
 
-template <bool kRootTie, class S>
-OTHM_FN void pop_ordered(Lane& L, S& stk) {
-    const int score = (L.flags & kPassed) ? L.alpha : -L.alpha;  // for the parent's mover
-    if (L.depth == 0) {
-        L.depth = -1;
-        L.value = -score;
-        return;
-    }
-    L.depth--;
-    u32 w;
-    stk.load(L.depth, L.P, L.O, L.M, L.alpha, L.beta, w);
-    L.flags = w & 0xFFu;
-    L.rem = (int)(w >> 8);
-    apply_score_ordered<kRootTie>(L, score);
+// take the next candidate off the mask
+template <class R>
+OTHM_FN u32 order_candidate(Order& Q) {
+    const u32 sq = R::lowest(Q.cand);
+    Q.cand &= Q.cand - 1;
+    return sq;
+}
+
+// the square to play: the pick just chosen, the single move, or rule 3's
+template <class R>
+OTHM_FN u32 order_choice(const Order& Q, u64 M) {
+    if (Q.pick < 64u) return Q.pick;
+    if ((M & (M - 1)) == 0) return R::lowest(M);
+    return static_pick<R>(M);
+}
+
+// THE SCORING STEP's end: the candidate's key against the running minimum
+OTHM_FN void order_keep(Order& Q, u32 key) {
+    if (key < Q.pick) Q.pick = key;
+    if (Q.cand == 0) Q.pick &= 63u;  // chosen: the next step plays it
 }
 
 // one step of the lane's ordered search; requires L.depth >= 0 and Q reset when
-// the position started.  advance()'s twin: its leaf, pass, game-over and push
-// code line for line (kept apart so that the unordered kernels compile from
-// the text they always had), with the pick of the header.
+// the position started.  search_core.hpp's pieces around the head above.
 template <class R, bool kRootTie, class S>
 OTHM_FN void advance_ordered(Lane& L, Order& Q, S& stk, const int* table, u32 limit) {
 #ifdef __HIPCC__
 #pragma unroll
 #endif
     for (int r = 0; r < kPopsPerStep; r++)
-        if (L.depth >= 0 && L.M == 0 && !(L.flags & (kFresh | kRootNew))) pop_ordered<kRootTie>(L, stk);
+        if (L.depth >= 0 && L.M == 0 && !(L.flags & (kFresh | kRootNew))) pop<kRootTie>(L, stk);
     if (L.depth < 0) return;
     u64 X, Y;  // the position to analyse: X to move
     const bool mv = L.M != 0;
@@ -127,21 +141,9 @@ OTHM_FN void advance_ordered(Lane& L, Order& Q, S& stk, const int* table, u32 li
     int lower = 0;  // 1: a root move below the best move, searched from alpha - 1
     if (mv) {
         if (L.nodes >= limit) return stop_at_limit(L);
-        if (Q.cand == 0 && Q.pick >= 64u && (L.M & (L.M - 1)) != 0 && L.rem >= kMobilityRem) {
-            Q.cand = L.M;  // begin a pick: this step scores its first candidate
-            Q.pick = ~0u;
-        }
+        order_begin(Q, L.M, [&] { return L.rem >= kMobilityRem; });
         scoring = Q.cand != 0;
-        if (scoring) {
-            sq = R::lowest(Q.cand);
-            Q.cand &= Q.cand - 1;
-        } else if (Q.pick < 64u) {
-            sq = Q.pick;
-        } else if ((L.M & (L.M - 1)) == 0) {
-            sq = R::lowest(L.M);
-        } else {
-            sq = static_pick<R>(L.M);
-        }
+        sq = scoring ? order_candidate<R>(Q) : order_choice<R>(Q, L.M);
         const u64 bit = 1ull << sq;
         const u64 f = R::flips(sq, L.P, L.O);
         X = L.O & ~f;
@@ -167,55 +169,9 @@ OTHM_FN void advance_ordered(Lane& L, Order& Q, S& stk, const int* table, u32 li
     const u64 cm = R::moves(X, Y);
     if (scoring) {
         const u32 corner = (kRegion0 >> sq) & 1u ? 0u : (u32)kCornerBonus;
-        const u32 key = (((u32)R::count(cm) + corner) << 6) | sq;
-        if (key < Q.pick) Q.pick = key;
-        if (Q.cand == 0) Q.pick &= 63u;  // chosen: the next step plays it
-        return;
+        return order_keep(Q, (((u32)R::count(cm) + corner) << 6) | sq);
     }
-    const u32 side = L.flags & kRootSide;
-    if (mv) {
-        if (L.rem <= 1 || ~(X | Y) == 0) {  // a leaf: scored here, nothing pushed
-            u64 om = 0;
-            if (side || cm == 0) om = R::moves(Y, X);
-            int score;
-            if ((cm | om) == 0) {
-                score = kTerminal * (R::count(Y) - R::count(X));
-            } else {
-                const int e = eval<R>(table, side ? Y : X, side ? om : cm, (u32)R::count(X | Y));
-                score = side ? e : -e;
-            }
-            apply_score_ordered<kRootTie>(L, score);  // (a leaf's score is exact: no window to widen)
-            return;
-        }
-        if (L.depth >= kFrames) return stop_at_limit(L);
-        stk.store(L.depth, L.P, L.O, L.M, L.alpha, L.beta, L.flags | ((u32)L.rem << 8));
-        L.depth++;
-        L.rem--;
-        L.P = X;
-        L.O = Y;
-        L.M = cm;
-        const int a = L.alpha - lower;
-        L.alpha = -L.beta;
-        L.beta = -a;
-        L.flags = (cm ? 0u : kFresh) | (side ^ kRootSide);
-    } else if (L.flags & kRootNew) {
-        L.M = cm;
-        L.flags = (cm ? 0u : kFresh) | kRootSide;
-    } else if (cm) {  // CHECK: a pass (no depth spent)
-        if (L.nodes >= limit) return stop_at_limit(L);
-        L.nodes++;
-        L.P = X;
-        L.O = Y;
-        L.M = cm;
-        const int a = L.alpha;
-        L.alpha = -L.beta;
-        L.beta = -a;
-        L.flags = kPassed | (side ^ kRootSide);
-        if (L.depth == 0) L.best_mv = kPassMove;
-    } else {  // CHECK: game over; the next step pops the frame
-        L.flags = side;
-        L.alpha = kTerminal * (R::count(L.P) - R::count(L.O));
-    }
+    settle_child<R, kRootTie>(L, stk, table, limit, mv, X, Y, cm, lower);
 }
 
 }  // namespace othm

@@ -22,8 +22,8 @@
 // global atomics per finished game.
 //
 // play_ordered_kernel is the same loop with order_core.hpp's ordered search
-// inside (include/othello_order.h, order = 1; play_core.hpp's
-// advance_ordered()); both kernels are instances of play_body<>.
+// inside (include/othello_order.h, order = 1; play_core.hpp's advance() with
+// its flag set); both kernels are instances of play_body<>.
 //
 // Bounds: a lane's loop ends.  Every search is bounded by node_limit (at most
 // that many steps that count a node, a constant number of others per node);
@@ -33,18 +33,10 @@
 //
 // Geometry: one wave per block.  7 frames x 36 B x 64 lanes + the tables =
 // 16.1 KB of LDS per block, eight blocks in a CU's 160 KB (two waves per SIMD).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
-#include <algorithm>
-#include <atomic>
-
-#include "../../include/othello.h"
 #include "../../include/othello_play.h"
 #include "../../include/othello_search.h"
 #include "../../include/othello_order.h"
-#include "bitboard.hpp"
+#include "device_common.hpp"
 #include "play_core.hpp"
 
 static_assert(OTHM_MAX_DEPTH == othm::kMaxDepth && OTHM_SEARCHED == othm::kSearched &&
@@ -61,42 +53,12 @@ using othm::u32;
 using othm::u64;
 
 constexpr int kPlayBlock = 64;  // one wave
-constexpr int kRefillMin = 8;   // idle lanes that make a wave refill (solve.hip's measurement)
-
-struct DeviceRules {
-    static __device__ __forceinline__ u64 moves(u64 P, u64 O) { return oth::moves(P, O); }
-    static __device__ __forceinline__ u64 flips(u32 sq, u64 P, u64 O) { return oth::flips_carry(sq, P, O); }
-    static __device__ __forceinline__ u32 lowest(u64 m) { return (u32)__builtin_ctzll(m); }
-    static __device__ __forceinline__ int count(u64 x) { return __popcll(x); }
-    static __device__ __forceinline__ int mul(int w, int c) { return __mul24(w, c); }
-};
-
-// frames [depth][field][lane]; `base` already points at the lane's column
-struct LdsStack {
-    u32* base;
-    __device__ __forceinline__ u32* at(int depth) const { return base + depth * (othm::kFields * kPlayBlock); }
-    __device__ __forceinline__ void store(int depth, u64 P, u64 O, u64 M, int alpha, int beta, u32 w) {
-        u32* f = at(depth);
-        f[0 * kPlayBlock] = (u32)P;
-        f[1 * kPlayBlock] = (u32)(P >> 32);
-        f[2 * kPlayBlock] = (u32)O;
-        f[3 * kPlayBlock] = (u32)(O >> 32);
-        f[4 * kPlayBlock] = (u32)M;
-        f[5 * kPlayBlock] = (u32)(M >> 32);
-        f[6 * kPlayBlock] = (u32)alpha;
-        f[7 * kPlayBlock] = (u32)beta;
-        f[8 * kPlayBlock] = w;
-    }
-    __device__ __forceinline__ void load(int depth, u64& P, u64& O, u64& M, int& alpha, int& beta, u32& w) const {
-        const u32* f = at(depth);
-        P = (u64)f[0 * kPlayBlock] | ((u64)f[1 * kPlayBlock] << 32);
-        O = (u64)f[2 * kPlayBlock] | ((u64)f[3 * kPlayBlock] << 32);
-        M = (u64)f[4 * kPlayBlock] | ((u64)f[5 * kPlayBlock] << 32);
-        alpha = (int)f[6 * kPlayBlock];
-        beta = (int)f[7 * kPlayBlock];
-        w = f[8 * kPlayBlock];
-    }
-};
+using othd::DeviceRules;
+using othd::env_int;
+using othd::kRefillMin;
+using othd::status_of;
+using LdsStack = othd::LdsStack9<kPlayBlock>;
+static_assert(LdsStack::kFields == othm::kFields, "the frame's words");
 
 struct PlayArgs {
     const u64* start;
@@ -207,10 +169,7 @@ __device__ __forceinline__ void play_body(const PlayArgs& a) {
             }
         }
         if (G.live) {
-            if constexpr (kOrdered)
-                othp::advance_ordered<DeviceRules>(G, L, Q, stk, tables, a.match, rec);
-            else
-                othp::advance<DeviceRules>(G, L, stk, tables, a.match, rec);
+            othp::advance<DeviceRules, kOrdered>(G, L, Q, stk, tables, a.match, rec);
             if (!G.live) emit(a, idx, G);
         }
     }
@@ -219,33 +178,13 @@ __device__ __forceinline__ void play_body(const PlayArgs& a) {
 __global__ __launch_bounds__(kPlayBlock) void play_kernel(PlayArgs a) { play_body<false>(a); }
 __global__ __launch_bounds__(kPlayBlock) void play_ordered_kernel(PlayArgs a) { play_body<true>(a); }
 
-inline int status_of(hipError_t e) { return e == hipSuccess ? OTH_OK : -(int)e; }
-
-int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-
-// blocks of the play kernel (order 0) or the ordered one (1) a device holds at
-// once, resolved on first use
-constexpr int kMaxDevices = 64;
-std::atomic<int> g_resident[2][kMaxDevices];
+// one cache for play_kernel (order 0), one for the ordered kernel (1)
+othd::ResidentBlocks g_resident[2];
 
 int resident_blocks(int order) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) return -1;
-    int r = g_resident[order][dev].load(std::memory_order_acquire);
-    if (r > 0) return r;
-    int cus = 256, per_cu = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const void* kernel = order ? reinterpret_cast<const void*>(play_ordered_kernel)
                                : reinterpret_cast<const void*>(play_kernel);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kPlayBlock, 0);
-    (void)hipGetLastError();
-    r = std::max(cus, 1) * (per_cu > 0 ? per_cu : 4);
-    g_resident[order][dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
-    return r;
+    return g_resident[order].get(kernel, kPlayBlock);
 }
 
 int play_grid(int64_t n, int order) {

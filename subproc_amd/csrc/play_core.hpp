@@ -207,23 +207,20 @@ OTHM_FN void step(Game& G, othm::Lane& L, const Match& m, Out& out) {
 
 // One step of a live game's lane: of its search, and of the game when that
 // leaves the lane without one.  `tables`: A's widened eval table, then B's
-// (2 x othm::kEvalTable ints); each search reads its mover's.
-template <class R, class S, class Out>
-OTHM_FN void advance(Game& G, othm::Lane& L, S& stk, const int* tables, const Match& m, Out& out) {
-    if (L.depth >= 0) othm::advance<R>(L, stk, tables + othm::kEvalTable * (int)mover_player(G), m.limit);
-    if (L.depth < 0) step<R>(G, L, m, out);
-}
-
-// advance() with order_core.hpp's ordered search (both players use it; the games'
-// moves are the same).  Q: the lane's scoring state, reset with every new root.
-template <class R, class S, class Out>
-OTHM_FN void advance_ordered(Game& G, othm::Lane& L, othm::Order& Q, S& stk, const int* tables, const Match& m,
-                             Out& out) {
-    if (L.depth >= 0)
-        othm::advance_ordered<R, true>(L, Q, stk, tables + othm::kEvalTable * (int)mover_player(G), m.limit);
+// (2 x othm::kEvalTable ints); each search reads its mover's.  kOrdered: both
+// players search with order_core.hpp's machine (the games' moves are the same);
+// Q is the lane's scoring state, reset with every new root, and unused otherwise.
+template <class R, bool kOrdered, class S, class Out>
+OTHM_FN void advance(Game& G, othm::Lane& L, othm::Order& Q, S& stk, const int* tables, const Match& m, Out& out) {
+    if (L.depth >= 0) {
+        if constexpr (kOrdered)
+            othm::advance_ordered<R, true>(L, Q, stk, tables + othm::kEvalTable * (int)mover_player(G), m.limit);
+        else
+            othm::advance<R>(L, stk, tables + othm::kEvalTable * (int)mover_player(G), m.limit);
+    }
     if (L.depth < 0) {
         step<R>(G, L, m, out);
-        othm::order_reset(Q);
+        if constexpr (kOrdered) othm::order_reset(Q);
     }
 }
 

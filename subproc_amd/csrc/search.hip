@@ -23,17 +23,9 @@
 // Geometry: one wave per block.  7 frames x 36 B x 64 lanes + the table =
 // 15.9 KB of LDS per block, eight blocks in a CU's 160 KB (two waves per
 // SIMD).  The waves share nothing; the one barrier orders the table's fill.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
-#include <algorithm>
-#include <atomic>
-
-#include "../../include/othello.h"
 #include "../../include/othello_search.h"
 #include "../../include/othello_order.h"
-#include "bitboard.hpp"
+#include "device_common.hpp"
 #include "order_core.hpp"
 #include "search_core.hpp"
 
@@ -51,43 +43,12 @@ using othm::u32;
 using othm::u64;
 
 constexpr int kSearchBlock = 64;  // one wave
-constexpr int kRefillMin = 8;     // idle lanes that make a wave refill (solve.hip's measurement)
-
-struct DeviceRules {
-    static __device__ __forceinline__ u64 moves(u64 P, u64 O) { return oth::moves(P, O); }
-    static __device__ __forceinline__ u64 flips(u32 sq, u64 P, u64 O) { return oth::flips_carry(sq, P, O); }
-    static __device__ __forceinline__ u32 lowest(u64 m) { return (u32)__builtin_ctzll(m); }
-    static __device__ __forceinline__ int count(u64 x) { return __popcll(x); }
-    // int8 weight x count <= 64: exact in 24 bits, a full-rate multiply
-    static __device__ __forceinline__ int mul(int w, int c) { return __mul24(w, c); }
-};
-
-// frames [depth][field][lane]; `base` already points at the lane's column
-struct LdsStack {
-    u32* base;
-    __device__ __forceinline__ u32* at(int depth) const { return base + depth * (othm::kFields * kSearchBlock); }
-    __device__ __forceinline__ void store(int depth, u64 P, u64 O, u64 M, int alpha, int beta, u32 w) {
-        u32* f = at(depth);
-        f[0 * kSearchBlock] = (u32)P;
-        f[1 * kSearchBlock] = (u32)(P >> 32);
-        f[2 * kSearchBlock] = (u32)O;
-        f[3 * kSearchBlock] = (u32)(O >> 32);
-        f[4 * kSearchBlock] = (u32)M;
-        f[5 * kSearchBlock] = (u32)(M >> 32);
-        f[6 * kSearchBlock] = (u32)alpha;
-        f[7 * kSearchBlock] = (u32)beta;
-        f[8 * kSearchBlock] = w;
-    }
-    __device__ __forceinline__ void load(int depth, u64& P, u64& O, u64& M, int& alpha, int& beta, u32& w) const {
-        const u32* f = at(depth);
-        P = (u64)f[0 * kSearchBlock] | ((u64)f[1 * kSearchBlock] << 32);
-        O = (u64)f[2 * kSearchBlock] | ((u64)f[3 * kSearchBlock] << 32);
-        M = (u64)f[4 * kSearchBlock] | ((u64)f[5 * kSearchBlock] << 32);
-        alpha = (int)f[6 * kSearchBlock];
-        beta = (int)f[7 * kSearchBlock];
-        w = f[8 * kSearchBlock];
-    }
-};
+using othd::DeviceRules;
+using othd::env_int;
+using othd::kRefillMin;
+using othd::status_of;
+using LdsStack = othd::LdsStack9<kSearchBlock>;
+static_assert(LdsStack::kFields == othm::kFields, "the frame's words");
 
 struct SearchArgs {
     const u64* boards;
@@ -170,33 +131,13 @@ __device__ __forceinline__ void search_body(const SearchArgs& a) {
 __global__ __launch_bounds__(kSearchBlock) void search_kernel(SearchArgs a) { search_body<false>(a); }
 __global__ __launch_bounds__(kSearchBlock) void search_ordered_kernel(SearchArgs a) { search_body<true>(a); }
 
-inline int status_of(hipError_t e) { return e == hipSuccess ? OTH_OK : -(int)e; }
-
-int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-
-// blocks of the search kernel (order 0) or the ordered one (1) a device holds at
-// once, resolved on first use
-constexpr int kMaxDevices = 64;
-std::atomic<int> g_resident[2][kMaxDevices];
+// one cache for search_kernel (order 0), one for the ordered kernel (1)
+othd::ResidentBlocks g_resident[2];
 
 int resident_blocks(int order) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) return -1;
-    int r = g_resident[order][dev].load(std::memory_order_acquire);
-    if (r > 0) return r;
-    int cus = 256, per_cu = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const void* kernel = order ? reinterpret_cast<const void*>(search_ordered_kernel)
                                : reinterpret_cast<const void*>(search_kernel);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kSearchBlock, 0);
-    (void)hipGetLastError();
-    r = std::max(cus, 1) * (per_cu > 0 ? per_cu : 4);
-    g_resident[order][dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
-    return r;
+    return g_resident[order].get(kernel, kSearchBlock);
 }
 
 int search_grid(int64_t n, int order) {

@@ -135,11 +135,26 @@ OTHM_FN void apply_score(Lane& L, int score) {
     }
 }
 
-// (pop() and advance() have twins in order_core.hpp, pop_ordered() and
-// advance_ordered(): the same transitions with another choice of the next move.
-// A change to the leaf, pass, game-over or push code here belongs there too.)
+// a finished child's value with the ROOT TIE RULE of order_core.hpp's header
+// (kRootTie; off: apply_score, which is all the unordered machine needs)
+template <bool kRootTie>
+OTHM_FN void apply_score_tie(Lane& L, int score) {
+    if (kRootTie && L.depth == 0 && score == L.alpha && L.root_mv < L.best_mv && L.best_mv < 64u)
+        L.best_mv = L.root_mv;  // (the move was searched from alpha - 1: the score is exact)
+    apply_score(L, score);
+}
+
+// THE PIECES.  advance() below and order_core.hpp's advance_ordered() are ONE
+// machine with two choices of the next move.  Each is a head of its own (the
+// pops, then which square and the child's boards X, Y) in front of the step's
+// one R::moves call and settle_child(), which holds every transition that does
+// not depend on the choice: leaf, push, root step, pass, game over.  pop() and
+// apply_score_tie() take the root tie rule as a flag.  What keeps the unordered
+// kernels as they were is a comparison of their assembly with the build before
+// a change, not a second copy of this text.
+
 // POP: the current frame is done (M == 0, checked), its value is alpha
-template <class S>
+template <bool kRootTie, class S>
 OTHM_FN void pop(Lane& L, S& stk) {
     const int score = (L.flags & kPassed) ? L.alpha : -L.alpha;  // for the parent's mover
     if (L.depth == 0) {
@@ -152,20 +167,75 @@ OTHM_FN void pop(Lane& L, S& stk) {
     stk.load(L.depth, L.P, L.O, L.M, L.alpha, L.beta, w);
     L.flags = w & 0xFFu;
     L.rem = (int)(w >> 8);
-    apply_score(L, score);
+    apply_score_tie<kRootTie>(L, score);
 }
 
 constexpr int kPopsPerStep = 2;  // as the solver's
 
+// the step's second half.  mv: the head placed a move, (X, Y) is the child and
+// cm its mover's moves: a leaf is scored, anything else pushed; `lower` = 1
+// widens the child's beta by one (the root tie rule).  !mv: cm settles a new
+// root's mask, a pass or the game's end.
+template <class R, bool kRootTie, class S>
+OTHM_FN void settle_child(Lane& L, S& stk, const int* table, u32 limit, bool mv, u64 X, u64 Y, u64 cm, int lower) {
+    const u32 side = L.flags & kRootSide;
+    if (mv) {
+        if (L.rem <= 1 || ~(X | Y) == 0) {  // a leaf: scored here, nothing pushed
+            // side != 0: the root side has just moved (it owns Y) and X's owner is to move
+            u64 om = 0;
+            if (side || cm == 0) om = R::moves(Y, X);
+            int score;
+            if ((cm | om) == 0) {
+                score = kTerminal * (R::count(Y) - R::count(X));
+            } else {
+                const int e = eval<R>(table, side ? Y : X, side ? om : cm, (u32)R::count(X | Y));
+                score = side ? e : -e;
+            }
+            apply_score_tie<kRootTie>(L, score);  // (a leaf's score is exact: no window to widen)
+            return;
+        }
+        // (rem <= kMaxDepth at the root and one less per push, so depth <=
+        // kFrames - 1 here; the check keeps a defect out of the neighbours' frames)
+        if (L.depth >= kFrames) return stop_at_limit(L);
+        stk.store(L.depth, L.P, L.O, L.M, L.alpha, L.beta, L.flags | ((u32)L.rem << 8));
+        L.depth++;
+        L.rem--;
+        L.P = X;
+        L.O = Y;
+        L.M = cm;
+        const int a = L.alpha - lower;
+        L.alpha = -L.beta;
+        L.beta = -a;
+        L.flags = (cm ? 0u : kFresh) | (side ^ kRootSide);
+    } else if (L.flags & kRootNew) {
+        L.M = cm;
+        L.flags = (cm ? 0u : kFresh) | kRootSide;
+    } else if (cm) {  // CHECK: a pass (no depth spent)
+        if (L.nodes >= limit) return stop_at_limit(L);
+        L.nodes++;
+        L.P = X;
+        L.O = Y;
+        L.M = cm;
+        const int a = L.alpha;
+        L.alpha = -L.beta;
+        L.beta = -a;
+        L.flags = kPassed | (side ^ kRootSide);
+        if (L.depth == 0) L.best_mv = kPassMove;
+    } else {  // CHECK: game over; the next step pops the frame
+        L.flags = side;
+        L.alpha = kTerminal * (R::count(L.P) - R::count(L.O));
+    }
+}
+
 // one step of the lane's search; requires L.depth >= 0.  `table`: the widened
-// eval table (kEvalTable ints)
+// eval table (kEvalTable ints).  The head: the lowest square of M.
 template <class R, class S>
 OTHM_FN void advance(Lane& L, S& stk, const int* table, u32 limit) {
 #ifdef __HIPCC__
 #pragma unroll
 #endif
     for (int r = 0; r < kPopsPerStep; r++)
-        if (L.depth >= 0 && L.M == 0 && !(L.flags & (kFresh | kRootNew))) pop(L, stk);
+        if (L.depth >= 0 && L.M == 0 && !(L.flags & (kFresh | kRootNew))) pop<false>(L, stk);
     if (L.depth < 0) return;
     u64 X, Y;  // the position to analyse: X to move
     const bool mv = L.M != 0;
@@ -189,53 +259,7 @@ OTHM_FN void advance(Lane& L, S& stk, const int* table, u32 limit) {
         return;  // a third finished frame in a row: the next step pops it
     }
     const u64 cm = R::moves(X, Y);
-    const u32 side = L.flags & kRootSide;
-    if (mv) {
-        if (L.rem <= 1 || ~(X | Y) == 0) {  // a leaf: scored here, nothing pushed
-            // side != 0: the root side has just moved (it owns Y) and X's owner is to move
-            u64 om = 0;
-            if (side || cm == 0) om = R::moves(Y, X);
-            int score;
-            if ((cm | om) == 0) {
-                score = kTerminal * (R::count(Y) - R::count(X));
-            } else {
-                const int e = eval<R>(table, side ? Y : X, side ? om : cm, (u32)R::count(X | Y));
-                score = side ? e : -e;
-            }
-            apply_score(L, score);
-            return;
-        }
-        // (rem <= kMaxDepth at the root and one less per push, so depth <=
-        // kFrames - 1 here; the check keeps a defect out of the neighbours' frames)
-        if (L.depth >= kFrames) return stop_at_limit(L);
-        stk.store(L.depth, L.P, L.O, L.M, L.alpha, L.beta, L.flags | ((u32)L.rem << 8));
-        L.depth++;
-        L.rem--;
-        L.P = X;
-        L.O = Y;
-        L.M = cm;
-        const int a = L.alpha;
-        L.alpha = -L.beta;
-        L.beta = -a;
-        L.flags = (cm ? 0u : kFresh) | (side ^ kRootSide);
-    } else if (L.flags & kRootNew) {
-        L.M = cm;
-        L.flags = (cm ? 0u : kFresh) | kRootSide;
-    } else if (cm) {  // CHECK: a pass (no depth spent)
-        if (L.nodes >= limit) return stop_at_limit(L);
-        L.nodes++;
-        L.P = X;
-        L.O = Y;
-        L.M = cm;
-        const int a = L.alpha;
-        L.alpha = -L.beta;
-        L.beta = -a;
-        L.flags = kPassed | (side ^ kRootSide);
-        if (L.depth == 0) L.best_mv = kPassMove;
-    } else {  // CHECK: game over; the next step pops the frame
-        L.flags = side;
-        L.alpha = kTerminal * (R::count(L.P) - R::count(L.O));
-    }
+    settle_child<R, false>(L, stk, table, limit, mv, X, Y, cm, 0);
 }
 
 }  // namespace othm

@@ -25,16 +25,8 @@
 // per block, eight blocks in a CU's 160 KB: two waves per SIMD, which this
 // dependent VALU chain wants (a 256-thread block would be alone on its CU, one
 // wave per SIMD).  The waves share nothing, so there is no barrier.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
-#include <algorithm>
-#include <atomic>
-
-#include "../../include/othello.h"
 #include "../../include/othello_solve.h"
-#include "bitboard.hpp"
+#include "device_common.hpp"
 #include "solve_core.hpp"
 
 static_assert(OTHS_MAX_EMPTIES == oths::kMaxEmpties, "header and core disagree");
@@ -48,37 +40,12 @@ using oths::u32;
 using oths::u64;
 
 constexpr int kSolveBlock = 64;  // one wave
-constexpr int kRefillMin = 8;    // idle lanes that make a wave refill (see above)
-
-struct DeviceRules {
-    static __device__ __forceinline__ u64 moves(u64 P, u64 O) { return oth::moves(P, O); }
-    static __device__ __forceinline__ u64 flips(u32 sq, u64 P, u64 O) { return oth::flips_carry(sq, P, O); }
-    static __device__ __forceinline__ u32 lowest(u64 m) { return (u32)__builtin_ctzll(m); }
-    static __device__ __forceinline__ int count(u64 x) { return __popcll(x); }
-};
-
-// frames [depth][field][lane]; `base` already points at the lane's column
-struct LdsStack {
-    u32* base;
-    __device__ __forceinline__ u32* at(int depth) const { return base + depth * (oths::kFields * kSolveBlock); }
-    __device__ __forceinline__ void store(int depth, u64 P, u64 O, u64 M, u32 w) {
-        u32* f = at(depth);
-        f[0 * kSolveBlock] = (u32)P;
-        f[1 * kSolveBlock] = (u32)(P >> 32);
-        f[2 * kSolveBlock] = (u32)O;
-        f[3 * kSolveBlock] = (u32)(O >> 32);
-        f[4 * kSolveBlock] = (u32)M;
-        f[5 * kSolveBlock] = (u32)(M >> 32);
-        f[6 * kSolveBlock] = w;
-    }
-    __device__ __forceinline__ void load(int depth, u64& P, u64& O, u64& M, u32& w) const {
-        const u32* f = at(depth);
-        P = (u64)f[0 * kSolveBlock] | ((u64)f[1 * kSolveBlock] << 32);
-        O = (u64)f[2 * kSolveBlock] | ((u64)f[3 * kSolveBlock] << 32);
-        M = (u64)f[4 * kSolveBlock] | ((u64)f[5 * kSolveBlock] << 32);
-        w = f[6 * kSolveBlock];
-    }
-};
+using othd::DeviceRules;
+using othd::env_int;
+using othd::kRefillMin;
+using othd::status_of;
+using LdsStack = othd::LdsStack7<kSolveBlock>;
+static_assert(LdsStack::kFields == oths::kFields, "the frame's words");
 
 struct SolveArgs {
     const u64* boards;
@@ -148,35 +115,10 @@ __global__ __launch_bounds__(kSolveBlock) void solve_kernel(SolveArgs a) {
     }
 }
 
-inline int status_of(hipError_t e) { return e == hipSuccess ? OTH_OK : -(int)e; }
-
-int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-
-// blocks of the solve kernel a device holds at once, resolved on first use
-constexpr int kMaxDevices = 64;
-std::atomic<int> g_resident[kMaxDevices];
-
-int resident_blocks() {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) return -1;
-    int r = g_resident[dev].load(std::memory_order_acquire);
-    if (r > 0) return r;
-    int cus = 256, per_cu = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(solve_kernel),
-                                                       kSolveBlock, 0);
-    (void)hipGetLastError();
-    r = std::max(cus, 1) * (per_cu > 0 ? per_cu : 4);
-    g_resident[dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
-    return r;
-}
+othd::ResidentBlocks g_resident;
 
 int solve_grid(int64_t n) {
-    const int resident = resident_blocks();
+    const int resident = g_resident.get(reinterpret_cast<const void*>(solve_kernel), kSolveBlock);
     if (resident <= 0) return -1;
     const int cap = std::min(std::max(env_int("OTH_SOLVE_BLOCKS", resident), 1), resident);
     return (int)std::min<int64_t>((n + kSolveBlock - 1) / kSolveBlock, (int64_t)cap);

@@ -135,37 +135,18 @@ OTHS_FN void pop(Lane& L, S& stk) {
 // cover nearly every case; a third waits for the next step)
 constexpr int kPopsPerStep = 2;
 
-// one step of the lane's search; requires L.depth >= 0
+// THE PIECES.  advance() below and solve_order_core.hpp's advance_ordered() are
+// ONE machine with two choices of the next move.  Each is a head of its own
+// (the pops, then which square and the child's boards X, Y) in front of the
+// step's one R::moves call and settle_child(), which holds every transition
+// that does not depend on the choice: board full, push, root step, pass, game
+// over.  What keeps solve_kernel as it was is a comparison of its assembly with
+// the build before a change, not a second copy of this text.
+
+// the step's second half.  mv: the head placed a move, (X, Y) is the child and
+// cm its mover's moves; !mv: cm settles a new root's mask, a pass or the game's end
 template <class R, class S>
-OTHS_FN void advance(Lane& L, S& stk, u32 limit) {
-#ifdef __HIPCC__
-#pragma unroll
-#endif
-    for (int r = 0; r < kPopsPerStep; r++)
-        if (L.depth >= 0 && L.M == 0 && !(L.flags & (kFresh | kRootNew))) pop(L, stk);
-    if (L.depth < 0) return;
-    u64 X, Y;  // the position to analyse: X to move
-    const bool mv = L.M != 0;
-    if (mv) {
-        if (L.nodes >= limit) return stop_at_limit(L);
-        const u32 sq = R::lowest(L.M);
-        const u64 bit = 1ull << sq;
-        L.M &= L.M - 1;
-        const u64 f = R::flips(sq, L.P, L.O);
-        X = L.O & ~f;
-        Y = L.P | f | bit;
-        if (L.depth == 0) L.root_mv = sq;
-        L.nodes++;
-    } else if (L.flags & kRootNew) {
-        X = L.P;
-        Y = L.O;
-    } else if (L.flags & kFresh) {
-        X = L.O;
-        Y = L.P;
-    } else {
-        return;  // a third finished frame in a row: the next step pops it
-    }
-    const u64 cm = R::moves(X, Y);
+OTHS_FN void settle_child(Lane& L, S& stk, u32 limit, bool mv, u64 X, u64 Y, u64 cm) {
     if (mv) {
         if (~(X | Y) == 0) {  // board full: the child's value for us, nothing pushed
             apply_score(L, R::count(Y) - R::count(X));
@@ -201,6 +182,41 @@ OTHS_FN void advance(Lane& L, S& stk, u32 limit) {
         L.flags = 0;
         L.alpha = R::count(L.P) - R::count(L.O);
     }
+}
+
+// one step of the lane's search; requires L.depth >= 0.  The head: the lowest
+// square of M.
+template <class R, class S>
+OTHS_FN void advance(Lane& L, S& stk, u32 limit) {
+#ifdef __HIPCC__
+#pragma unroll
+#endif
+    for (int r = 0; r < kPopsPerStep; r++)
+        if (L.depth >= 0 && L.M == 0 && !(L.flags & (kFresh | kRootNew))) pop(L, stk);
+    if (L.depth < 0) return;
+    u64 X, Y;  // the position to analyse: X to move
+    const bool mv = L.M != 0;
+    if (mv) {
+        if (L.nodes >= limit) return stop_at_limit(L);
+        const u32 sq = R::lowest(L.M);
+        const u64 bit = 1ull << sq;
+        L.M &= L.M - 1;
+        const u64 f = R::flips(sq, L.P, L.O);
+        X = L.O & ~f;
+        Y = L.P | f | bit;
+        if (L.depth == 0) L.root_mv = sq;
+        L.nodes++;
+    } else if (L.flags & kRootNew) {
+        X = L.P;
+        Y = L.O;
+    } else if (L.flags & kFresh) {
+        X = L.O;
+        Y = L.P;
+    } else {
+        return;  // a third finished frame in a row: the next step pops it
+    }
+    const u64 cm = R::moves(X, Y);
+    settle_child<R>(L, stk, limit, mv, X, Y, cm);
 }
 
 // what a position is before any search (kSolved: search it); empties = the

@@ -1,8 +1,9 @@
 // solve_order_core.hpp — solve_core.hpp's state machine with MOVE ORDERING: the
-// same frames, Lane, start_task() and pop(), a different choice of the next
+// same frames, Lane, pop() and settle_child(), a different choice of the next
 // move.  Written once for the device (solve_tree.hip's ordered task kernel) and
-// the host (tools/diag/solve_tree_host.cpp with order = 1).  DESIGN.md §17;
-// the search's twin is order_core.hpp (§16).
+// the host (tools/diag/solve_tree_host.cpp with order = 1).  The choice is made
+// by order_core.hpp's pieces (§16), the very functions the search's ordered
+// machine uses, with this file's size test for the mobility order.  DESIGN.md §17.
 //
 // THE RULE (the contract of `order = 1` inside a task).  A frame with moves
 // left picks:
@@ -17,7 +18,7 @@
 // There is no root tie rule: a task's depth-0 frame is an inner tree node, and
 // the tree's root reads its move off its children (solve_tree_core.hpp).
 //
-// THE SCORING STEP is §16's: a step takes ONE candidate off the register-held
+// THE SCORING STEP is order_core.hpp's: a step takes ONE candidate off the register-held
 // mask Order::cand, does one flips and one moves for it and keeps the running
 // minimum in Order::pick as (score + 3) << 6 | square; the step that empties
 // the mask leaves the chosen square in `pick`, the FOLLOWING step plays it.
@@ -46,9 +47,7 @@ namespace oths {
 constexpr int kMobilityEmpties = OTHS_MOBILITY_EMPTIES;
 
 // one step of the lane's ordered search; requires L.depth >= 0 and Q reset when
-// the task started.  advance()'s twin: its pass, game-over and push code line
-// for line (kept apart so that solve_kernel compiles from the text it always
-// had), with the pick of the header.
+// the task started.  solve_core.hpp's pieces around order_core.hpp's head.
 template <class R, class S>
 OTHS_FN void advance_ordered(Lane& L, othm::Order& Q, S& stk, u32 limit) {
 #ifdef __HIPCC__
@@ -63,22 +62,9 @@ OTHS_FN void advance_ordered(Lane& L, othm::Order& Q, S& stk, u32 limit) {
     u32 sq = 0;
     if (mv) {
         if (L.nodes >= limit) return stop_at_limit(L);
-        if (Q.cand == 0 && Q.pick >= 64u && (L.M & (L.M - 1)) != 0 &&
-            64 - R::count(L.P | L.O) >= kMobilityEmpties) {
-            Q.cand = L.M;  // begin a pick: this step scores its first candidate
-            Q.pick = ~0u;
-        }
+        othm::order_begin(Q, L.M, [&] { return 64 - R::count(L.P | L.O) >= kMobilityEmpties; });
         scoring = Q.cand != 0;
-        if (scoring) {
-            sq = R::lowest(Q.cand);
-            Q.cand &= Q.cand - 1;
-        } else if (Q.pick < 64u) {
-            sq = Q.pick;
-        } else if ((L.M & (L.M - 1)) == 0) {
-            sq = R::lowest(L.M);
-        } else {
-            sq = othm::static_pick<R>(L.M);
-        }
+        sq = scoring ? othm::order_candidate<R>(Q) : othm::order_choice<R>(Q, L.M);
         const u64 bit = 1ull << sq;
         const u64 f = R::flips(sq, L.P, L.O);
         X = L.O & ~f;
@@ -101,44 +87,9 @@ OTHS_FN void advance_ordered(Lane& L, othm::Order& Q, S& stk, u32 limit) {
     const u64 cm = R::moves(X, Y);
     if (scoring) {
         const u32 corner = (othm::kRegion0 >> sq) & 1u ? 0u : (u32)othm::kCornerBonus;
-        const u32 key = (((u32)R::count(cm) + corner) << 6) | sq;
-        if (key < Q.pick) Q.pick = key;
-        if (Q.cand == 0) Q.pick &= 63u;  // chosen: the next step plays it
-        return;
+        return othm::order_keep(Q, (((u32)R::count(cm) + corner) << 6) | sq);
     }
-    if (mv) {
-        if (~(X | Y) == 0) {  // board full: the child's value for us, nothing pushed
-            apply_score(L, R::count(Y) - R::count(X));
-            return;
-        }
-        if (L.depth >= kFrames) return stop_at_limit(L);
-        stk.store(L.depth, L.P, L.O, L.M, pack(L.alpha, L.beta, L.flags));
-        L.depth++;
-        L.P = X;
-        L.O = Y;
-        L.M = cm;
-        const int a = L.alpha;
-        L.alpha = -L.beta;
-        L.beta = -a;
-        L.flags = cm ? 0u : kFresh;
-    } else if (L.flags & kRootNew) {
-        L.M = cm;
-        L.flags = cm ? 0u : kFresh;
-    } else if (cm) {  // CHECK: a pass
-        if (L.nodes >= limit) return stop_at_limit(L);
-        L.nodes++;
-        L.P = X;
-        L.O = Y;
-        L.M = cm;
-        const int a = L.alpha;
-        L.alpha = -L.beta;
-        L.beta = -a;
-        L.flags = kPassed;
-        if (L.depth == 0) L.best_mv = kPassMove;
-    } else {  // CHECK: game over; the next step pops the frame
-        L.flags = 0;
-        L.alpha = R::count(L.P) - R::count(L.O);
-    }
+    settle_child<R>(L, stk, limit, mv, X, Y, cm);
 }
 
 }  // namespace oths

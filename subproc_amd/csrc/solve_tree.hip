@@ -21,17 +21,9 @@
 // atomics only; the immutable node fields cross a kernel boundary.  No lane
 // waits for another: every loop is bounded by the tree's height, by the
 // children of one node or by node_limit.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
-#include <algorithm>
-#include <atomic>
-
-#include "../../include/othello.h"
 #include "../../include/othello_solve.h"
 #include "../../include/othello_solve_tree.h"
-#include "bitboard.hpp"
+#include "device_common.hpp"
 #include "solve_order_core.hpp"
 #include "solve_tree_core.hpp"
 
@@ -49,57 +41,18 @@ using othe::u32;
 using othe::u64;
 
 constexpr int kTaskBlock = 64;     // one wave
-constexpr int kRefillMin = 8;      // idle lanes that make a wave refill (solve.hip's measurement)
 constexpr int kExpandBlock = 256;
 // true: a task's window comes from the state words as they are when it starts;
 // false: from the expansion's snapshot
 constexpr bool kShareBounds = true;
 
-struct DeviceRules {
-    static __device__ __forceinline__ u64 moves(u64 P, u64 O) { return oth::moves(P, O); }
-    static __device__ __forceinline__ u64 flips(u32 sq, u64 P, u64 O) { return oth::flips_carry(sq, P, O); }
-    static __device__ __forceinline__ u32 lowest(u64 m) { return (u32)__builtin_ctzll(m); }
-    static __device__ __forceinline__ int count(u64 x) { return __popcll(x); }
-};
-
-struct DeviceAtomics {
-    static __device__ __forceinline__ u64 load(u64* p) {
-        return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    static __device__ __forceinline__ bool cas(u64* p, u64& expected, u64 desired) {
-        return __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // an exchange whose return the lane waits for: the word is in place before
-    // the lane's next atomic is issued
-    static __device__ __forceinline__ void store(u64* p, u64 v) {
-        const u64 old = __hip_atomic_exchange(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("" ::"v"(old) : "memory");
-    }
-};
-
-// frames [depth][field][lane]; `base` already points at the lane's column
-struct LdsStack {
-    u32* base;
-    __device__ __forceinline__ u32* at(int depth) const { return base + depth * (oths::kFields * kTaskBlock); }
-    __device__ __forceinline__ void store(int depth, u64 P, u64 O, u64 M, u32 w) {
-        u32* f = at(depth);
-        f[0 * kTaskBlock] = (u32)P;
-        f[1 * kTaskBlock] = (u32)(P >> 32);
-        f[2 * kTaskBlock] = (u32)O;
-        f[3 * kTaskBlock] = (u32)(O >> 32);
-        f[4 * kTaskBlock] = (u32)M;
-        f[5 * kTaskBlock] = (u32)(M >> 32);
-        f[6 * kTaskBlock] = w;
-    }
-    __device__ __forceinline__ void load(int depth, u64& P, u64& O, u64& M, u32& w) const {
-        const u32* f = at(depth);
-        P = (u64)f[0 * kTaskBlock] | ((u64)f[1 * kTaskBlock] << 32);
-        O = (u64)f[2 * kTaskBlock] | ((u64)f[3 * kTaskBlock] << 32);
-        M = (u64)f[4 * kTaskBlock] | ((u64)f[5 * kTaskBlock] << 32);
-        w = f[6 * kTaskBlock];
-    }
-};
+using othd::DeviceAtomics;
+using othd::DeviceRules;
+using othd::env_int;
+using othd::kRefillMin;
+using othd::status_of;
+using LdsStack = othd::LdsStack7<kTaskBlock>;
+static_assert(LdsStack::kFields == oths::kFields, "the frame's words");
 
 // per position, beside its slab
 struct PosHdr {
@@ -299,7 +252,13 @@ struct TaskArgs {
     u32 limit;
 };
 
-// (split_solve_tasks_ordered below is this loop again with the ordered machine: a change here belongs there too)
+// The persistent loop of the task launch.  It is written out twice:
+// split_solve_tasks_ordered below is this text with the scoring state Q beside
+// the lane's L and solve_order_core.hpp's machine inside a task, and a change to one is
+// a change to both.  search.hip's and play.hip's pairs are instances of one
+// body; these are not, because a kernel that calls its loop compiles to other
+// code than a kernel that is its loop (DESIGN.md §16 has the comparison that
+// decides such things).
 __global__ __launch_bounds__(kTaskBlock) void split_solve_tasks(TaskArgs a) {
     __shared__ u32 frames[oths::kFrames * oths::kFields * kTaskBlock];
     const u32 lane = threadIdx.x;
@@ -379,9 +338,6 @@ __global__ __launch_bounds__(kTaskBlock) void split_solve_tasks(TaskArgs a) {
     }
 }
 
-// split_solve_tasks with solve_order_core.hpp's machine inside a task (order =
-// 1): the same loop, the scoring state Q beside the lane's L.  Kept as a kernel
-// of its own text, as tree.hip's pair is.
 __global__ __launch_bounds__(kTaskBlock) void split_solve_tasks_ordered(TaskArgs a) {
     __shared__ u32 frames[oths::kFrames * oths::kFields * kTaskBlock];
     const u32 lane = threadIdx.x;
@@ -464,33 +420,13 @@ __global__ __launch_bounds__(kTaskBlock) void split_solve_tasks_ordered(TaskArgs
     }
 }
 
-inline int status_of(hipError_t e) { return e == hipSuccess ? OTH_OK : -(int)e; }
-
-int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-
-// blocks of the task kernel (order 0) or the ordered one (1) a device holds at
-// once, resolved on first use
-constexpr int kMaxDevices = 64;
-std::atomic<int> g_resident[2][kMaxDevices];
+// one cache for split_solve_tasks (order 0), one for the ordered kernel (1)
+othd::ResidentBlocks g_resident[2];
 
 int resident_blocks(int order) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) return -1;
-    int r = g_resident[order][dev].load(std::memory_order_acquire);
-    if (r > 0) return r;
-    int cus = 256, per_cu = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const void* kernel = order ? reinterpret_cast<const void*>(split_solve_tasks_ordered)
                                : reinterpret_cast<const void*>(split_solve_tasks);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kTaskBlock, 0);
-    (void)hipGetLastError();
-    r = std::max(cus, 1) * (per_cu > 0 ? per_cu : 4);
-    g_resident[order][dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
-    return r;
+    return g_resident[order].get(kernel, kTaskBlock);
 }
 
 int task_grid(int64_t tasks, int order) {

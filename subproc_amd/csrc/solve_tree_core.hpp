@@ -16,17 +16,15 @@
 // final nor expanded; each is searched by solve_core.hpp's advance() or
 // solve_order_core.hpp's advance_ordered() and has at most 12 empties.
 //
-// One 64-bit state word per node is all that tasks share:
-//   bits 63..32  best value so far, from the node's mover's side (int32, -65..64)
-//   bit  31      a task below met the node limit (sticky on the way up)
-//   bits 30..0   children not finished yet
-// It is read and written by the atomics of the template parameter A only
-// (agent scope on the device).  Everything else in a node is written by the
-// expansion launch and only read afterwards.
+// The state word that the tasks share (its best value here in -65..64), the
+// back-up, the windows and the root's answer are split_tree_common.hpp's; this
+// file keeps what the solver's tree alone has: a node with its empties, values
+// without a scale, the window's ends, its task.
 #pragma once
 #include <stdint.h>
 
 #include "solve_core.hpp"
+#include "split_tree_common.hpp"
 
 #ifdef __HIPCC__
 #define OTHE_FN __device__ __forceinline__
@@ -48,10 +46,14 @@ constexpr int kMaxRounds = 2 * kMaxEmpties + 2;
 // halves of a frame's packed window hold
 constexpr int kInf = 65;
 
-constexpr u32 kFinal = 1;  // neither side can move: the value is in the state word
-
-constexpr u64 kLimitBit = 1ull << 31;
-constexpr u64 kCountMask = kLimitBit - 1;
+using othx::best_of;
+using othx::count_of;
+using othx::fold;
+using othx::fold_up;
+using othx::is_task;
+using othx::kFinal;
+using othx::kLimitBit;
+using othx::pack;
 
 struct Node {
     u64 P, O, M;      // the mover's discs, the opponent's, the mover's moves
@@ -65,10 +67,7 @@ struct Node {
     int32_t snap;     // best after the expansion's own back-up: the "nothing shared" windows
 };
 static_assert(sizeof(Node) == 48, "node layout");
-
-OTHE_FN u64 pack(int best, u64 low) { return ((u64)(u32)best << 32) | low; }
-OTHE_FN int best_of(u64 w) { return (int)(u32)(w >> 32); }
-OTHE_FN u32 count_of(u64 w) { return (u32)(w & kCountMask); }
+static_assert(othx::kNoMove == oths::kNoMove && othx::kPassMove == oths::kPassMove, "move codes");
 
 template <class R>
 OTHE_FN void make_node(Node& c, u64 P, u64 O, int parent, u32 move) {
@@ -99,71 +98,14 @@ OTHE_FN u32 child_count(const Node& x, int task_empties) {
 template <class R>
 OTHE_FN void expand(Node* slab, u32 i, u32 first, u32 cnt) {
     const Node x = slab[i];
-    if (x.M == 0) {
-        make_node<R>(slab[first], x.O, x.P, (int)i, oths::kPassMove);
-    } else {
-        u32 k = first;
-        for (u64 m = x.M; m; m &= m - 1, k++) {
-            const u32 sq = R::lowest(m);
-            const u64 f = R::flips(sq, x.P, x.O);
-            make_node<R>(slab[k], x.O & ~f, x.P | f | (1ull << sq), (int)i, sq);
-        }
-    }
-    slab[i].first_child = first;
-    slab[i].nchild = (uint8_t)cnt;
-    slab[i].state = pack(-kInf, cnt);
+    othx::place_children<R, kInf>(slab, x, i, first, cnt,
+                                  [&](Node& c, u64 P, u64 O, u32 move, int) { make_node<R>(c, P, O, (int)i, move); });
 }
 
-OTHE_FN bool is_task(const Node& x) { return !(x.flags & kFinal) && x.nchild == 0; }
-
-// fold the finished child's value v (from ITS mover's side) into node p's
-// word; returns the new word
-template <class A>
-OTHE_FN u64 fold(Node* slab, u32 p, int v, u64 lim) {
-    u64 old = A::load(&slab[p].state), nw;
-    do {
-        const int b = best_of(old);
-        nw = pack(-v > b ? -v : b, ((old | lim) & kLimitBit) | (u64)(count_of(old) - 1u));
-    } while (!A::cas(&slab[p].state, old, nw));
-    return nw;
-}
-
-// task i (never the root) is finished with value v: carry it up as far as nodes
-// complete.  True when the root completed.  Bounded by the tree's height.
-template <class A>
-OTHE_FN bool fold_up(Node* slab, u32 i, int v, u64 lim) {
-    A::store(&slab[i].state, pack(v, lim));  // a task's own word: the root's scan reads its children's
-    for (;;) {
-        const u32 p = (u32)slab[i].parent;
-        const u64 w = fold<A>(slab, p, v, lim);
-        if (count_of(w) != 0) return false;
-        if (slab[p].parent < 0) return true;
-        i = p;
-        v = best_of(w);
-        lim = w & kLimitBit;
-    }
-}
-
-// the window of task t from its ancestors' words, in t's mover's view: an
-// ancestor an even number of edges up bounds alpha by its best, an odd one
-// bounds beta by minus its best.  The ROOT hands down best - 1, so that a root
-// child that ties the maximum still comes back exact (the tie rule).  With
-// `shared` false the bests are the expansion's snapshot.  Both ends lie in
-// -65..65.
+// split_tree_common.hpp's window; both ends lie in -65..65
 template <class A>
 OTHE_FN void window(Node* slab, u32 t, bool shared, int& alpha, int& beta) {
-    alpha = -kInf;
-    beta = kInf;
-    bool odd = true;
-    for (int i = slab[t].parent; i >= 0; i = slab[i].parent, odd = !odd) {
-        int b = shared ? best_of(A::load(&slab[i].state)) : (int)slab[i].snap;
-        if (slab[i].parent < 0 && b > -kInf) b--;
-        if (odd) {
-            if (-b < beta) beta = -b;
-        } else if (b > alpha) {
-            alpha = b;
-        }
-    }
+    othx::window<A, kInf>(slab, t, shared, alpha, beta);
 }
 
 // a task enters the solver's state machine past its kRootNew step
@@ -185,28 +127,7 @@ OTHE_FN void start_task(oths::Lane& L, const Node& x, int alpha, int beta) {
 // the completed root's answer
 template <class A>
 OTHE_FN void root_result(Node* slab, int& value, u32& move, u32& status) {
-    const u64 w = A::load(&slab[0].state);
-    if (w & kLimitBit) {
-        value = 0;
-        move = oths::kNoMove;
-        status = oths::kLimit;
-        return;
-    }
-    value = best_of(w);
-    status = oths::kSolved;
-    if (slab[0].flags & kFinal) {
-        move = oths::kNoMove;
-    } else if (slab[0].M == 0) {
-        move = oths::kPassMove;
-    } else {
-        move = oths::kNoMove;
-        const u32 f = slab[0].first_child, e = f + slab[0].nchild;
-        for (u32 c = f; c < e; c++)
-            if (-best_of(A::load(&slab[c].state)) == value) {
-                move = slab[c].move;
-                break;
-            }
-    }
+    othx::root_result<A>(slab, oths::kSolved, oths::kLimit, value, move, status);
 }
 
 }  // namespace othe

@@ -24,18 +24,10 @@
 // atomics only; the immutable node fields cross a kernel boundary.  No lane
 // waits for another: every loop is bounded by the tree's height or by the
 // children of one node.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
-#include <algorithm>
-#include <atomic>
-
-#include "../../include/othello.h"
 #include "../../include/othello_search.h"
 #include "../../include/othello_tree.h"
 #include "../../include/othello_order.h"
-#include "bitboard.hpp"
+#include "device_common.hpp"
 #include "order_core.hpp"
 #include "tree_core.hpp"
 
@@ -52,62 +44,18 @@ using otht::u32;
 using otht::u64;
 
 constexpr int kTaskBlock = 64;     // one wave
-constexpr int kRefillMin = 8;      // idle lanes that make a wave refill (solve.hip's measurement)
 constexpr int kExpandBlock = 256;
 // true: a task's window comes from the state words as they are when it starts;
 // false: from the expansion's snapshot (tools/diag/tree_snapshot.patch)
 constexpr bool kShareBounds = true;
 
-struct DeviceRules {
-    static __device__ __forceinline__ u64 moves(u64 P, u64 O) { return oth::moves(P, O); }
-    static __device__ __forceinline__ u64 flips(u32 sq, u64 P, u64 O) { return oth::flips_carry(sq, P, O); }
-    static __device__ __forceinline__ u32 lowest(u64 m) { return (u32)__builtin_ctzll(m); }
-    static __device__ __forceinline__ int count(u64 x) { return __popcll(x); }
-    static __device__ __forceinline__ int mul(int w, int c) { return __mul24(w, c); }
-};
-
-struct DeviceAtomics {
-    static __device__ __forceinline__ u64 load(u64* p) {
-        return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    static __device__ __forceinline__ bool cas(u64* p, u64& expected, u64 desired) {
-        return __hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                    __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // an exchange whose return the lane waits for: the word is in place before
-    // the lane's next atomic is issued
-    static __device__ __forceinline__ void store(u64* p, u64 v) {
-        const u64 old = __hip_atomic_exchange(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("" ::"v"(old) : "memory");
-    }
-};
-
-// frames [depth][field][lane]; `base` already points at the lane's column
-struct LdsStack {
-    u32* base;
-    __device__ __forceinline__ u32* at(int depth) const { return base + depth * (othm::kFields * kTaskBlock); }
-    __device__ __forceinline__ void store(int depth, u64 P, u64 O, u64 M, int alpha, int beta, u32 w) {
-        u32* f = at(depth);
-        f[0 * kTaskBlock] = (u32)P;
-        f[1 * kTaskBlock] = (u32)(P >> 32);
-        f[2 * kTaskBlock] = (u32)O;
-        f[3 * kTaskBlock] = (u32)(O >> 32);
-        f[4 * kTaskBlock] = (u32)M;
-        f[5 * kTaskBlock] = (u32)(M >> 32);
-        f[6 * kTaskBlock] = (u32)alpha;
-        f[7 * kTaskBlock] = (u32)beta;
-        f[8 * kTaskBlock] = w;
-    }
-    __device__ __forceinline__ void load(int depth, u64& P, u64& O, u64& M, int& alpha, int& beta, u32& w) const {
-        const u32* f = at(depth);
-        P = (u64)f[0 * kTaskBlock] | ((u64)f[1 * kTaskBlock] << 32);
-        O = (u64)f[2 * kTaskBlock] | ((u64)f[3 * kTaskBlock] << 32);
-        M = (u64)f[4 * kTaskBlock] | ((u64)f[5 * kTaskBlock] << 32);
-        alpha = (int)f[6 * kTaskBlock];
-        beta = (int)f[7 * kTaskBlock];
-        w = f[8 * kTaskBlock];
-    }
-};
+using othd::DeviceAtomics;
+using othd::DeviceRules;
+using othd::env_int;
+using othd::kRefillMin;
+using othd::status_of;
+using LdsStack = othd::LdsStack9<kTaskBlock>;
+static_assert(LdsStack::kFields == othm::kFields, "the frame's words");
 
 // per position, beside its slab
 struct PosHdr {
@@ -308,7 +256,13 @@ struct TaskArgs {
     int8_t w[OTH_EVAL_WEIGHTS];
 };
 
-// (task_ordered_kernel below is this loop again with the ordered machine: a change here belongs there too)
+// The persistent loop of the task launch.  It is written out twice:
+// task_ordered_kernel below is this text with the scoring state Q beside
+// the lane's L and order_core.hpp's machine inside a task, and a change to one is
+// a change to both.  search.hip's and play.hip's pairs are instances of one
+// body; these are not, because a kernel that calls its loop compiles to other
+// code than a kernel that is its loop (DESIGN.md §16 has the comparison that
+// decides such things).
 __global__ __launch_bounds__(kTaskBlock) void task_kernel(TaskArgs a) {
     __shared__ u32 frames[othm::kFrames * othm::kFields * kTaskBlock];
     __shared__ int table[othm::kEvalTable];
@@ -391,10 +345,6 @@ __global__ __launch_bounds__(kTaskBlock) void task_kernel(TaskArgs a) {
     }
 }
 
-// task_kernel with order_core.hpp's machine inside a task (otho_tree_ordered,
-// order = 1): the same loop, the scoring state Q beside the lane's L, the root
-// tie rule off (a task's depth-0 frame is a tree node).  Kept as
-// a kernel of its own text so that task_kernel compiles to what it always was.
 __global__ __launch_bounds__(kTaskBlock) void task_ordered_kernel(TaskArgs a) {
     __shared__ u32 frames[othm::kFrames * othm::kFields * kTaskBlock];
     __shared__ int table[othm::kEvalTable];
@@ -480,33 +430,13 @@ __global__ __launch_bounds__(kTaskBlock) void task_ordered_kernel(TaskArgs a) {
     }
 }
 
-inline int status_of(hipError_t e) { return e == hipSuccess ? OTH_OK : -(int)e; }
-
-int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-
-// blocks of the task kernel (order 0) or the ordered one (1) a device holds at
-// once, resolved on first use
-constexpr int kMaxDevices = 64;
-std::atomic<int> g_resident[2][kMaxDevices];
+// one cache for task_kernel (order 0), one for the ordered kernel (1)
+othd::ResidentBlocks g_resident[2];
 
 int resident_blocks(int order) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= kMaxDevices) return -1;
-    int r = g_resident[order][dev].load(std::memory_order_acquire);
-    if (r > 0) return r;
-    int cus = 256, per_cu = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const void* kernel = order ? reinterpret_cast<const void*>(task_ordered_kernel)
                                : reinterpret_cast<const void*>(task_kernel);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kTaskBlock, 0);
-    (void)hipGetLastError();
-    r = std::max(cus, 1) * (per_cu > 0 ? per_cu : 4);
-    g_resident[order][dev].store(r, std::memory_order_release);  // (racing first calls compute the same value)
-    return r;
+    return g_resident[order].get(kernel, kTaskBlock);
 }
 
 int task_grid(int64_t tasks, int order) {

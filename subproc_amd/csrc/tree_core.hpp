@@ -12,17 +12,15 @@
 // made.  The tasks are the nodes that are neither final nor expanded; each is
 // searched by search_core.hpp's advance() with `rem` plies (1..8).
 //
-// One 64-bit state word per node is all that tasks share:
-//   bits 63..32  best value so far, from the node's mover's side (int32)
-//   bit  31      a task below met the node limit (sticky on the way up)
-//   bits 30..0   children not finished yet
-// It is read and written by the atomics of the template parameter A only
-// (agent scope on the device).  Everything else in a node is written by the
-// expansion launch and only read afterwards.
+// The state word that the tasks share, the back-up, the windows and the
+// root's answer are split_tree_common.hpp's, which the split solver's tree
+// (solve_tree_core.hpp) uses too; this file keeps what the search's tree alone
+// has: a node with plies left and a side, its values' scale, its task.
 #pragma once
 #include <stdint.h>
 
 #include "search_core.hpp"
+#include "split_tree_common.hpp"
 
 #ifdef __HIPCC__
 #define OTHT_FN __device__ __forceinline__
@@ -41,11 +39,16 @@ constexpr int kMinNodes = 64;           // nodes_per_position's lower bound: the
 constexpr int kMaxRounds = 2 * kMaxSplit + 1;  // a pass and a placement alternate at worst
 constexpr int kInf = othm::kInf;
 
-constexpr u32 kFinal = 1;     // neither side can move: the value is in the state word
+using othx::kFinal;           // flag 1
 constexpr u32 kSideRoot = 2;  // the node's mover is the root mover
 
-constexpr u64 kLimitBit = 1ull << 31;
-constexpr u64 kCountMask = kLimitBit - 1;
+using othx::best_of;
+using othx::count_of;
+using othx::fold;
+using othx::fold_up;
+using othx::is_task;
+using othx::kLimitBit;
+using othx::pack;
 
 struct Node {
     u64 P, O, M;      // the mover's discs, the opponent's, the mover's moves
@@ -59,10 +62,7 @@ struct Node {
     int32_t snap;     // best after the expansion's own back-up: the "nothing shared" windows
 };
 static_assert(sizeof(Node) == 48, "node layout");
-
-OTHT_FN u64 pack(int best, u64 low) { return ((u64)(u32)best << 32) | low; }
-OTHT_FN int best_of(u64 w) { return (int)(u32)(w >> 32); }
-OTHT_FN u32 count_of(u64 w) { return (u32)(w & kCountMask); }
+static_assert(othx::kNoMove == othm::kNoMove && othx::kPassMove == othm::kPassMove, "move codes");
 
 template <class R>
 OTHT_FN void make_node(Node& c, u64 P, u64 O, int parent, u32 move, int rem, u32 side) {
@@ -93,70 +93,15 @@ template <class R>
 OTHT_FN void expand(Node* slab, u32 i, u32 first, u32 cnt) {
     const Node x = slab[i];
     const u32 side = (x.flags & kSideRoot) ^ kSideRoot;
-    if (x.M == 0) {
-        make_node<R>(slab[first], x.O, x.P, (int)i, othm::kPassMove, x.rem, side);
-    } else {
-        u32 k = first;
-        for (u64 m = x.M; m; m &= m - 1, k++) {
-            const u32 sq = R::lowest(m);
-            const u64 f = R::flips(sq, x.P, x.O);
-            make_node<R>(slab[k], x.O & ~f, x.P | f | (1ull << sq), (int)i, sq, x.rem - 1, side);
-        }
-    }
-    slab[i].first_child = first;
-    slab[i].nchild = (uint8_t)cnt;
-    slab[i].state = pack(-kInf, cnt);
+    othx::place_children<R, kInf>(slab, x, i, first, cnt, [&](Node& c, u64 P, u64 O, u32 move, int spent) {
+        make_node<R>(c, P, O, (int)i, move, x.rem - spent, side);
+    });
 }
 
-OTHT_FN bool is_task(const Node& x) { return !(x.flags & kFinal) && x.nchild == 0; }
-
-// fold the finished child's value v (from ITS mover's side) into node p's
-// word; returns the new word
-template <class A>
-OTHT_FN u64 fold(Node* slab, u32 p, int v, u64 lim) {
-    u64 old = A::load(&slab[p].state), nw;
-    do {
-        const int b = best_of(old);
-        nw = pack(-v > b ? -v : b, ((old | lim) & kLimitBit) | (u64)(count_of(old) - 1u));
-    } while (!A::cas(&slab[p].state, old, nw));
-    return nw;
-}
-
-// task i (never the root) is finished with value v: carry it up as far as nodes
-// complete.  True when the root completed.  Bounded by the tree's height.
-template <class A>
-OTHT_FN bool fold_up(Node* slab, u32 i, int v, u64 lim) {
-    A::store(&slab[i].state, pack(v, lim));  // a task's own word: the root's scan reads its children's
-    for (;;) {
-        const u32 p = (u32)slab[i].parent;
-        const u64 w = fold<A>(slab, p, v, lim);
-        if (count_of(w) != 0) return false;
-        if (slab[p].parent < 0) return true;
-        i = p;
-        v = best_of(w);
-        lim = w & kLimitBit;
-    }
-}
-
-// the window of task t from its ancestors' words, in t's mover's view: an
-// ancestor an even number of edges up bounds alpha by its best, an odd one
-// bounds beta by minus its best.  The ROOT hands down best - 1, so that a root
-// child that ties the maximum still comes back exact (the tie rule).  With
-// `shared` false the bests are the expansion's snapshot.
+// split_tree_common.hpp's window, inside (-kInf, kInf)
 template <class A>
 OTHT_FN void window(Node* slab, u32 t, bool shared, int& alpha, int& beta) {
-    alpha = -kInf;
-    beta = kInf;
-    bool odd = true;
-    for (int i = slab[t].parent; i >= 0; i = slab[i].parent, odd = !odd) {
-        int b = shared ? best_of(A::load(&slab[i].state)) : (int)slab[i].snap;
-        if (slab[i].parent < 0 && b > -kInf) b--;
-        if (odd) {
-            if (-b < beta) beta = -b;
-        } else if (b > alpha) {
-            alpha = b;
-        }
-    }
+    othx::window<A, kInf>(slab, t, shared, alpha, beta);
 }
 
 // a task enters the state machine past its kRootNew step
@@ -179,28 +124,7 @@ OTHT_FN void start_task(othm::Lane& L, const Node& x, int alpha, int beta) {
 // the completed root's answer
 template <class A>
 OTHT_FN void root_result(Node* slab, int& value, u32& move, u32& status) {
-    const u64 w = A::load(&slab[0].state);
-    if (w & kLimitBit) {
-        value = 0;
-        move = othm::kNoMove;
-        status = othm::kLimit;
-        return;
-    }
-    value = best_of(w);
-    status = othm::kSearched;
-    if (slab[0].flags & kFinal) {
-        move = othm::kNoMove;
-    } else if (slab[0].M == 0) {
-        move = othm::kPassMove;
-    } else {
-        move = othm::kNoMove;
-        const u32 f = slab[0].first_child, e = f + slab[0].nchild;
-        for (u32 c = f; c < e; c++)
-            if (-best_of(A::load(&slab[c].state)) == value) {
-                move = slab[c].move;
-                break;
-            }
-    }
+    othx::root_result<A>(slab, othm::kSearched, othm::kLimit, value, move, status);
 }
 
 }  // namespace otht

@@ -29,73 +29,13 @@
 
 #include "../../subproc_amd/csrc/solve_order_core.hpp"
 #include "../../subproc_amd/csrc/solve_tree_core.hpp"
+#include "host_rules.hpp"
 
 using othe::Node;
 using othe::u32;
 using othe::u64;
 
-// the rules, stated over whole boards one direction at a time (the 16-empties
-// roots need a host build that makes some ten million nodes a second)
-struct HostRules {
-    // a board moved one square in direction d: east, south-west, south, south-east, then their opposites
-    static u64 step(u64 x, int d) {
-        switch (d) {
-            case 0: return (x << 1) & 0xFEFEFEFEFEFEFEFEull;
-            case 1: return (x << 7) & 0x7F7F7F7F7F7F7F7Full;
-            case 2: return x << 8;
-            case 3: return (x << 9) & 0xFEFEFEFEFEFEFEFEull;
-            case 4: return (x >> 1) & 0x7F7F7F7F7F7F7F7Full;
-            case 5: return (x >> 7) & 0xFEFEFEFEFEFEFEFEull;
-            case 6: return x >> 8;
-            default: return (x >> 9) & 0x7F7F7F7F7F7F7F7Full;
-        }
-    }
-    static int count(u64 x) { return __builtin_popcountll(x); }
-    static u32 lowest(u64 m) { return (u32)__builtin_ctzll(m); }
-    // the opponent discs the move on empty square sq turns over
-    static u64 flips(u32 sq, u64 P, u64 O) {
-        u64 all = 0;
-        for (int d = 0; d < 8; d++) {
-            u64 run = 0, x = step(1ull << sq, d);
-            while (x & O) {
-                run |= x;
-                x = step(x, d);
-            }
-            if (x & P) all |= run;
-        }
-        return all;
-    }
-    // the empty squares from which a run of O ends on a disc of P
-    static u64 moves(u64 P, u64 O) {
-        u64 m = 0;
-        for (int d = 0; d < 8; d++) {
-            u64 run = step(P, d) & O;
-            for (int k = 0; k < 5; k++) run |= step(run, d) & O;
-            m |= step(run, d);
-        }
-        return m & ~(P | O);
-    }
-};
-
-struct HostAtomics {
-    static u64 load(u64* p) { return *p; }
-    static bool cas(u64* p, u64& expected, u64 desired) {
-        if (*p != expected) {
-            expected = *p;
-            return false;
-        }
-        *p = desired;
-        return true;
-    }
-    static void store(u64* p, u64 v) { *p = v; }
-};
-
-struct HostStack {
-    u64 P[oths::kFrames], O[oths::kFrames], M[oths::kFrames];
-    u32 w[oths::kFrames];
-    void store(int d, u64 p, u64 o, u64 m, u32 ww) { P[d] = p, O[d] = o, M[d] = m, w[d] = ww; }
-    void load(int d, u64& p, u64& o, u64& m, u32& ww) const { p = P[d], o = O[d], m = M[d], ww = w[d]; }
-};
+using HostStack = HostStack7<oths::kFrames>;
 
 struct Pos {
     u64 black, white;

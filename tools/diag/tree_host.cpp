@@ -26,65 +26,13 @@
 
 #include "../../subproc_amd/csrc/order_core.hpp"
 #include "../../subproc_amd/csrc/tree_core.hpp"
+#include "host_rules.hpp"
 
 using otht::Node;
 using otht::u32;
 using otht::u64;
 
-struct HostRules {
-    static constexpr int dx[8] = {1, -1, 0, 0, 1, -1, -1, 1};
-    static constexpr int dy[8] = {0, 0, 1, -1, 1, -1, 1, -1};
-    static int count(u64 x) { return __builtin_popcountll(x); }
-    static u32 lowest(u64 m) { return (u32)__builtin_ctzll(m); }
-    static int mul(int w, int c) { return w * c; }
-    static u64 flips(u32 sq, u64 P, u64 O) {
-        u64 all = 0;
-        for (int d = 0; d < 8; d++) {
-            int x = (int)(sq & 7) + dx[d], y = (int)(sq >> 3) + dy[d];
-            u64 run = 0;
-            while (x >= 0 && x < 8 && y >= 0 && y < 8 && (O >> (x + 8 * y) & 1)) {
-                run |= 1ull << (x + 8 * y);
-                x += dx[d];
-                y += dy[d];
-            }
-            if (run && x >= 0 && x < 8 && y >= 0 && y < 8 && (P >> (x + 8 * y) & 1)) all |= run;
-        }
-        return all;
-    }
-    static u64 moves(u64 P, u64 O) {
-        u64 m = 0;
-        for (u64 e = ~(P | O); e; e &= e - 1) {
-            const u32 sq = lowest(e);
-            if (flips(sq, P, O)) m |= 1ull << sq;
-        }
-        return m;
-    }
-};
-
-struct HostAtomics {
-    static u64 load(u64* p) { return *p; }
-    static bool cas(u64* p, u64& expected, u64 desired) {
-        if (*p != expected) {
-            expected = *p;
-            return false;
-        }
-        *p = desired;
-        return true;
-    }
-    static void store(u64* p, u64 v) { *p = v; }
-};
-
-struct HostStack {
-    u64 P[othm::kFrames], O[othm::kFrames], M[othm::kFrames];
-    int a[othm::kFrames], b[othm::kFrames];
-    u32 w[othm::kFrames];
-    void store(int d, u64 p, u64 o, u64 m, int al, int be, u32 ww) {
-        P[d] = p, O[d] = o, M[d] = m, a[d] = al, b[d] = be, w[d] = ww;
-    }
-    void load(int d, u64& p, u64& o, u64& m, int& al, int& be, u32& ww) const {
-        p = P[d], o = O[d], m = M[d], al = a[d], be = b[d], ww = w[d];
-    }
-};
+using HostStack = HostStack9<othm::kFrames>;
 
 struct Pos {
     u64 black, white;
