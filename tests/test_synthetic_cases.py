@@ -1,0 +1,400 @@
+"""tests/synthetic_cases.py's claims about its own positions, checked with the C
+oracle and the exhaustive checkers alone, and the five host drivers of the
+searches' cores (tools/diag/{solve,search,tree,solve_tree,play}_host.cpp: plain
+C++ rules, plain loads and stores) against the checkers on every family: a rules
+bug in a *_core.hpp shows here, before any GPU run.  The two tree drivers run
+every position's tasks in four orders (forward, reverse, shuffled, nothing
+shared); every driver runs with order 0 and 1.  CPU only."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import oracle
+import play_ref
+import search_ref
+import solve_cases
+import solve_ref
+import synthetic_cases as sc
+import tree_cases
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DRIVERS = ("solve", "search", "tree", "solve_tree", "play")
+SOLVED = SEARCHED = 1
+SKIPPED, NOROOM = 0, 4
+NODE_LIMIT = 1 << 22
+THREADS = 8
+SOLVE_TREE_DEFAULT_NODES, TREE_DEFAULT_NODES = 65536, 32768
+T = sc.T
+GAME_KEYS = ("a_black", "final_boards", "diff", "plies", "status", "moves")
+
+
+# ---------------------------------------------------------------- the generator's claims
+@pytest.mark.parametrize("family,e", [(f, e) for f in sorted(sc.FAMILIES) for e in (4, 6, 8, 12, 20, 40, 52)
+                                      if f != "islands" or e <= 8])
+def test_families_are_disjoint_with_the_empties_asked_and_both_movers(family, e):
+    b, t = sc.FAMILIES[family](e)
+    assert len(t) == (sc.ISLANDS_DEEP_ROOTS if family == "islands" and e > 6 else sc.ROOTS)
+    assert ((b[:, 0] & b[:, 1]) == 0).all() and (solve_ref.empties(b) == e).all()
+    assert set(t.tolist()) == {1, 2} and not b.flags.writeable and not t.flags.writeable
+    assert len(np.unique(b, axis=0)) == len(b)
+    if family == "centre":
+        assert ((b[:, 0] | b[:, 1]) & np.uint64(sc._mask(sc.CENTRE)) == 0).all()
+    if family == "islands":
+        assert (sc.cut_off(b) >= (2 if e >= 6 else 1)).all()
+    if family == "lopsided":
+        share = sc.popcount(b[:, 0]) / (64.0 - e)
+        for k, want in enumerate(sc.SHARES):
+            assert abs(share[k::4].mean() - want) < 0.03
+            assert set(t[k::4].tolist()) == {1, 2}
+
+
+def test_the_rollout_pool_has_no_such_boards():
+    """The centre squares are never empty in a game, and two empty squares
+    without an occupied neighbour are rare near its end (none of the pool's
+    2,078 positions at 4 empties, 0.3 % at 6, 0.9 % at 8)."""
+    centre = np.uint64(sc._mask(sc.CENTRE))
+    for p in solve_cases.pool().values():
+        assert (((p["boards"][:, 0] | p["boards"][:, 1]) & centre) == centre).all()
+    for e in (4, 6, 8):
+        assert (sc.cut_off(solve_cases.pool()[e]["boards"]) >= 2).mean() < 0.01
+
+
+@pytest.mark.parametrize("e", [6, 8])
+def test_lopsided_roots_pass_and_end(e):
+    fp, over = sc.root_kinds(*sc.lopsided(e))
+    assert fp.sum() >= 8 and over.sum() >= 8
+    # (measured: 13 and 13 at 6 empties, 11 and 16 at 8; the 8-empties rollout case has 8 of both kinds together)
+    c = solve_cases.cases()[8]
+    assert int(c["forced_pass"].sum() + c["over"].sum()) <= 8
+
+
+def test_lopsided_values_go_further_than_uniform_ones():
+    lv = sc.solver_reference("lopsided8")[0]
+    uv = sc.solver_reference("uniform8")[0]
+    assert np.abs(lv).max() >= 58 and np.abs(uv).max() <= 48  # (61 and 44)
+
+
+def test_lopsided_trees_hold_more_passes_than_the_rollouts():
+    """Per node of the whole trees: 69,586 inner passes in 435,741 nodes (0.160)
+    against 0.103 in the trees of the last 16 roots of solve_cases.cases()[8].
+    Per root it is the other way round, 544 against 1,352: the lopsided trees
+    are a quarter of the size, most of their lines end early."""
+    b, t = sc.solver_inputs("lopsided8")
+    passes, _, _, nodes = sc.census(b, t, 16)
+    assert passes.sum() == sc.solver_reference("lopsided8")[2]  # the checker's count
+    c = solve_cases.cases()[8]
+    rp, _, _, rn = sc.census(c["boards"][-16:], c["turn"][-16:], 16)
+    assert passes.sum() / nodes.sum() > rp.sum() / rn.sum()
+    assert passes.sum() / len(t) < c["inner_passes"] / len(c["turn"])
+
+
+def test_wide_roots_have_28_moves_or_more():
+    b, t = sc.wide()
+    moves = sc.popcount(oracle.legal(b, t))
+    assert len(t) == 16 and (moves >= sc.WIDE_MIN).all() and set(t.tolist()) == {1, 2}
+    assert ((b[:, 0] & b[:, 1]) == 0).all()
+    assert sc.wide_max() == 35 and moves.max() == 34  # the midgame roots of the other tests have at most 21
+    assert sc.popcount(oracle.legal(tree_cases.midgame()["boards"], tree_cases.midgame()["turn"])).max() == 21
+    assert len(sc.wide(32)[1]) == 32 and (sc.wide(32)[0][:16] == b).all()
+
+
+def test_every_islands_root_can_end_with_empties_left():
+    for e in (4, 6, 8):
+        b, t = sc.islands(e)
+        assert sc.census(b, t, 2 * e)[2].all()
+
+
+@pytest.mark.parametrize("name", ["lopsided6_d9", "lopsided8_d9", "islands6_d9", "islands8_d9"])
+def test_split_cases_pass_and_end_inside_the_split_plies(name):
+    """Split 4: a node that must pass at levels 1..3, a game-over node at
+    levels 1..4.  Measured, roots with a pass / with a final: lopsided 81 / 20
+    at 6 empties and 68 / 19 at 8, islands 42 / 9 at 6 and 19 / 0 at 8: no
+    islands(8) game ends within four plies (it would leave four empties or
+    more), so that case has passes only and islands(6) stands in for the finals."""
+    b, t = sc.search_inputs(name)
+    passes, finals, _, _ = sc.census(b, t, 4)
+    assert (passes > 0).sum() >= 8
+    assert (finals > 0).sum() >= (0 if name == "islands8_d9" else 8)
+    fp, over = sc.root_kinds(b, t)
+    assert fp.sum() + over.sum() >= (8 if name.startswith("lopsided") else 1)
+
+
+def test_islands_end_inside_the_solvers_split_plies():
+    """The split solver expands down to task_empties = 1: every level of an
+    islands(6) tree, game-overs with empties included."""
+    b, t = sc.islands(6)
+    _, finals, with_empties, _ = sc.census(b, t, 5)
+    assert (finals > 0).sum() >= 8 and with_empties.sum() >= 8
+
+
+def test_the_edges_are_what_their_names_say():
+    b, t, names = sc.edges()
+    assert len(t) == 2 * len(sc.EDGES) == 20 and ((b[:, 0] & b[:, 1]) == 0).all()
+    own, opp = oracle.legal(b, t), oracle.legal(b, (3 - t).astype(np.uint8))
+    emp = solve_ref.empties(b)
+    for name, e in (("empty", 64), ("one disc", 63), ("two adjacent discs", 62), ("full black", 0), ("full white", 0),
+                    ("full 63:1", 0), ("full 32:32", 0), ("four unplayable empties", 4)):
+        for turn in (1, 2):
+            i = sc.edge(name, turn)
+            assert names[i] == name and t[i] == turn and emp[i] == e and own[i] == 0 and opp[i] == 0, (name, turn)
+    i = sc.edge("wipe-out", 1)
+    assert own[i] == 1 and emp[i] == 2  # a1, and it leaves White without a disc
+    after = oracle.step(b[i:i + 1], t[i:i + 1], np.array([0], np.uint8))["boards"]
+    assert after[0, 1] == 0 and sc.popcount(after[:, 0])[0] == 63
+    i = sc.edge("pass then the last move", 1)
+    assert own[i] == 0 and opp[i] == 1 and emp[i] == 1
+    v, m, _ = solve_ref.solve(b, t)
+    want = {("full black", 1): 64, ("full black", 2): -64, ("full white", 1): -64, ("full 63:1", 1): 62,
+            ("full 63:1", 2): -62, ("full 32:32", 1): 0, ("empty", 1): 0, ("wipe-out", 1): 63,
+            ("four unplayable empties", 1): 3 - 57}
+    for (name, turn), value in want.items():
+        assert v[sc.edge(name, turn)] == value, (name, turn)
+    assert m[sc.edge("wipe-out", 1)] == 0 and m[sc.edge("pass then the last move", 1)] == 64
+    assert (m[:16] == 255).all()
+
+
+def test_images_are_the_16_images():
+    b, t = sc.uniform(30)
+    ib, it, perm = sc.images(b[:4], t[:4])
+    assert ib.shape == (64, 2) and it.shape == (64,) and perm.shape == (64, 64)
+    assert (np.sort(perm, axis=1) == np.arange(64)).all()
+    assert (ib[0] == b[0]).all() and it[0] == t[0] and (perm[0] == np.arange(64)).all()  # the identity comes first
+    assert (ib[8] == b[0, ::-1]).all() and it[8] == 3 - t[0]
+    for j in range(64):
+        src = b[j // 16, ::-1] if j % 16 >= 8 else b[j // 16]
+        for c in (0, 1):
+            assert int(ib[j, c]) == sc._mask(perm[j][s] for s in range(64) if int(src[c]) >> s & 1)
+    assert len(np.unique(ib[:16], axis=0)) == 16
+    # legal moves move with the squares
+    own = oracle.legal(ib, it)
+    root = oracle.legal(b[:4], t[:4])
+    for j in range(64):
+        assert int(own[j]) == sc._mask(perm[j][s] for s in range(64) if int(root[j // 16]) >> s & 1)
+
+
+def test_the_eval_is_the_same_on_all_16_images():
+    """The region masks are symmetric and the eval is from the given side: what
+    the GPU file's metamorphic tests rely on.  (It is not antisymmetric in the
+    side: an image's value is equal, not opposite, because the mover swaps too.)"""
+    for e in (10, 30, 52):
+        b, t = sc.uniform(e)
+        ib, it, _ = sc.images(b[:16], t[:16])
+        for w in sc.TABLES.values():
+            ev = oracle.evaluate(ib, it, w).reshape(16, 16)
+            assert (ev == ev[:, :1]).all()
+            assert len(np.unique(ev[:, 0])) > 8
+
+
+def test_the_tied_roots():
+    for kind, roots in (("solve", 8), ("search", 5)):  # 13 tied roots: at least 8 are asked for
+        b, t, v, m = sc.tie_roots(kind)
+        assert len(t) == 16 * roots
+        v, m = v.reshape(-1, 16), m.reshape(-1, 16)
+        assert (v == v[:, :1]).all()
+        assert all(len(set(row.tolist())) > 1 for row in m)
+
+
+# ---------------------------------------------------------------- the host drivers
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    d = tmp_path_factory.mktemp("synthetic_host")
+    exe = {}
+    for name in DRIVERS:
+        exe[name] = str(d / (name + "_host"))
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fopenmp", "-o", exe[name],
+                               os.path.join(ROOT, "tools", "diag", name + "_host.cpp")])
+    return exe
+
+
+def write_positions(path, boards, turn):
+    with open(path, "w") as f:
+        for (b, w), t in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist()):
+            f.write("%x %x %d\n" % (b, w, t))
+
+
+def write_weights(path, weights):
+    with open(path, "w") as f:
+        f.write(" ".join(str(int(x)) for x in np.asarray(weights).reshape(-1)) + "\n")
+
+
+def read_rows(path, orders):
+    rows = np.array([[int(x) for x in ln.split()] for ln in open(path)], np.int64)
+    if orders == 1:
+        return rows[:, 0], rows[:, 1], rows[:, 2]
+    rows = rows.reshape(-1, orders, 4)
+    return tuple(rows[:, :, k].T for k in range(3))
+
+
+def run_driver(exe, tmp_path, boards, turn, args, weights=None, orders=1):
+    """(value, move, status) of a driver: [n], or [4 task orders][n] for the two tree drivers."""
+    inp, out, wf = (str(tmp_path / x) for x in ("in", "out", "w"))
+    write_positions(inp, boards, turn)
+    head = [exe, inp, out]
+    if weights is not None:
+        write_weights(wf, weights)
+        head.append(wf)
+    subprocess.run(head + [str(a) for a in args], check=True, stderr=subprocess.DEVNULL)
+    return read_rows(out, orders)
+
+
+def solve_host(host, tmp_path, boards, turn, max_empties=12):
+    return run_driver(host["solve"], tmp_path, boards, turn, [max_empties, NODE_LIMIT, THREADS])
+
+
+def solve_tree_host(host, tmp_path, boards, turn, task_empties, npp, order, max_empties=16):
+    return run_driver(host["solve_tree"], tmp_path, boards, turn,
+                      [max_empties, task_empties, npp, NODE_LIMIT, 7, order, THREADS], orders=4)
+
+
+def search_host(host, tmp_path, boards, turn, depth, table, order):
+    return run_driver(host["search"], tmp_path, boards, turn, [depth, NODE_LIMIT, THREADS, order], sc.TABLES[table])
+
+
+def tree_host(host, tmp_path, boards, turn, depth, split, table, order, npp=TREE_DEFAULT_NODES):
+    return run_driver(host["tree"], tmp_path, boards, turn, [depth, split, npp, NODE_LIMIT, 1, order],
+                      sc.TABLES[table], orders=4)
+
+
+def play_host(host, tmp_path, name, order, boards=None, turn=None, depth=None, exact=None, seed=None):
+    c = sc.PLAY[name] if name else dict(depth=depth, exact=exact, seed=seed)
+    if boards is None:
+        boards, turn = sc.play_starts(name)
+    args, out = str(tmp_path / "args"), str(tmp_path / "out")
+    with open(args, "w") as f:
+        f.write("%d %d %d %d %d %d %d %d %d %d %d\n" % (len(turn), c["seed"], 0, c["depth"][0], c["depth"][1],
+                                                     c["exact"], 0, 0, 1, NODE_LIMIT, 1))
+        for w in ("default", "rng7"):
+            f.write(" ".join(str(int(x)) for x in sc.TABLES[w].reshape(-1)) + "\n")
+        for (b, w), t in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist()):
+            f.write("%x %x %d\n" % (b, w, t))
+    subprocess.run([host["play"], args, out, str(THREADS), str(order)], check=True, stderr=subprocess.DEVNULL)
+    rows = [ln.split() for ln in open(out)]
+    return dict(a_black=np.array([int(r[0]) for r in rows], np.uint8),
+                final_boards=np.array([[int(r[1], 16), int(r[2], 16)] for r in rows], np.uint64).reshape(-1, 2),
+                diff=np.array([int(r[3]) for r in rows], np.int8), plies=np.array([int(r[4]) for r in rows], np.uint8),
+                status=np.array([int(r[5]) for r in rows], np.uint8),
+                moves=np.array([list(bytes.fromhex(r[7])) for r in rows], np.uint8).reshape(-1, 128))
+
+
+def same(got, want, what, status=SOLVED):
+    v, m, s = got
+    assert (s == status).all(), (what, np.nonzero(s != status)[0][:8])
+    bad = np.nonzero((v != want[0]) | (m != want[1]))[0]
+    assert len(bad) == 0, (what, bad[:8], v[bad[:8]], want[0][bad[:8]], m[bad[:8]], want[1][bad[:8]])
+
+
+def same_in_all_orders(got, want, what, status=SOLVED):
+    for o in range(4):
+        same(tuple(x[o] for x in got), want, (what, o), status)
+
+
+@pytest.mark.parametrize("name", sorted(sc.SOLVER))
+def test_solve_host_matches_the_checker(host, tmp_path, name):
+    b, t = sc.solver_inputs(name)
+    same(solve_host(host, tmp_path, b, t), sc.solver_reference(name), name)
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("name", sorted(sc.SOLVER))
+def test_solve_tree_host_matches_the_checker(host, tmp_path, name, order):
+    b, t = sc.solver_inputs(name)
+    for task_empties in (1, 3):
+        for npp in (64, SOLVE_TREE_DEFAULT_NODES):
+            got = solve_tree_host(host, tmp_path, b, t, task_empties, npp, order)
+            same_in_all_orders(got, sc.solver_reference(name), (name, task_empties, npp))
+
+
+def test_the_solvers_host_builds_on_the_edges(host, tmp_path):
+    b, t, names = sc.edges()
+    rv, rm, _ = solve_ref.solve(b, t)
+    small = solve_ref.empties(b) <= 12
+    want = (np.where(small, rv, 0), np.where(small, rm, 255))
+    status = np.where(small, SOLVED, SKIPPED)
+    v, m, s = solve_host(host, tmp_path, b, t)
+    assert (s == status).all() and (v == want[0]).all() and (m == want[1]).all()
+    for order in (0, 1):
+        for task_empties in (1, 3):
+            v, m, s = solve_tree_host(host, tmp_path, b, t, task_empties, 64, order)
+            for o in range(4):
+                assert (s[o] == status).all() and (v[o] == want[0]).all() and (m[o] == want[1]).all()
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("name", sorted(sc.SEARCH))
+def test_search_host_matches_the_checker(host, tmp_path, name, order):
+    _, depth, _, tables, _ = sc.SEARCH[name]
+    b, t = sc.search_inputs(name)
+    for table in tables:
+        same(search_host(host, tmp_path, b, t, depth, table, order), sc.search_reference(name, table), (name, table))
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("name", sorted(sc.SEARCH) + sorted(sc.TREE))
+def test_tree_host_matches_the_checker(host, tmp_path, name, order):
+    _, depth, _, tables, splits = sc.search_case(name)
+    b, t = sc.search_inputs(name)
+    for table in tables if name in sc.TREE or depth < 8 else ("default",):  # (full depth: no eval is taken)
+        for split in splits:
+            for npp in (TREE_DEFAULT_NODES,) if name == "wide5" else (TREE_DEFAULT_NODES, 64):
+                # (64 nodes: the tasks start higher; depth - 1 <= 8 plies are left below the root's level)
+                got = tree_host(host, tmp_path, b, t, depth, split, table, order, npp)
+                same_in_all_orders(got, sc.search_reference(name, table), (name, table, split, npp))
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("split", sc.NOROOM_SPLITS)
+def test_tree_host_has_no_room_exactly_where_the_rule_says(host, tmp_path, split, order):
+    b, t, rv, rm = sc.noroom_case()
+    want = tree_cases.expected_noroom(b, t, sc.NOROOM_DEPTH, split, sc.NOROOM_SLAB)
+    assert want.sum() == 16 and len(t) == 48 and (want == (sc.popcount(oracle.legal(b, t)) >= sc.WIDE_MIN)).all()
+    v, m, s = tree_host(host, tmp_path, b, t, sc.NOROOM_DEPTH, split, "default", order, sc.NOROOM_SLAB)
+    for o in range(4):
+        assert (s[o] == np.where(want, NOROOM, SEARCHED)).all()
+        assert (v[o] == rv).all() and (m[o] == rm).all()
+
+
+def test_the_searches_host_builds_on_the_edges(host, tmp_path):
+    b, t, names = sc.edges()
+    for table in ("default", "extreme"):
+        rv, rm, _ = search_ref.search(b, t, 3, sc.TABLES[table])
+        assert rv[sc.edge("full black", 1)] == 64 * T and rv[sc.edge("full white", 1)] == -64 * T
+        for order in (0, 1):
+            same(search_host(host, tmp_path, b, t, 3, table, order), (rv, rm), "edges")
+            same_in_all_orders(tree_host(host, tmp_path, b, t, 3, 2, table, order), (rv, rm), "edges")
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("name", sorted(sc.PLAY))
+def test_play_host_matches_the_checker(host, tmp_path, name, order):
+    got, ref = play_host(host, tmp_path, name, order), sc.play_reference(name)
+    for k in GAME_KEYS:
+        assert (got[k] == ref[k]).all(), (name, k)
+    if name.startswith("lopsided"):
+        assert (ref["plies"] == 0).any() and (ref["moves"] == 64).any()  # starts that are over; passes
+
+
+@pytest.mark.parametrize("order", [0, 1])
+def test_ties_in_the_host_builds(host, tmp_path, order):
+    """Every image against the checker run on that image, through all five."""
+    b, t, rv, rm = sc.tie_roots("solve")
+    same(solve_host(host, tmp_path, b, t), (rv, rm), "solve")
+    for task_empties in (1, 3):
+        same_in_all_orders(solve_tree_host(host, tmp_path, b, t, task_empties, 64, order), (rv, rm), "solve tree")
+    same(search_host(host, tmp_path, b, t, 6, "default", order), (T * rv, rm), "search, full depth")
+    for split in (1, 2, 3):
+        same_in_all_orders(tree_host(host, tmp_path, b, t, 6, split, "default", order), (T * rv, rm), "tree")
+    ref = play_ref.play(len(t), 300, play_ref.search_chooser(sc.TABLES["default"], sc.TABLES["rng7"], 2, 2, 6),
+                        swap=True, start=b, start_turn=t)
+    got = play_host(host, tmp_path, None, order, b, t, depth=(2, 2), exact=6, seed=300)
+    for k in GAME_KEYS:
+        assert (got[k] == ref[k]).all(), k
+    own = sc.popcount(oracle.legal(b, t))
+    assert (ref["moves"][own > 1, 0] == rm[own > 1]).all()  # the first move is the solver's, the tie rule's
+    b, t, rv, rm = sc.tie_roots("search")
+    same(search_host(host, tmp_path, b, t, sc.TIE_DEPTH, sc.TIE_TABLE, order), (rv, rm), "search")
+    same_in_all_orders(tree_host(host, tmp_path, b, t, sc.TIE_DEPTH, 1, sc.TIE_TABLE, order), (rv, rm), "tree")
