@@ -15,6 +15,7 @@ PLAY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_play.h")
 TREE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_tree.h")
 ORDER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_order.h")
 SOLVE_TREE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve_tree.h")
+SOLVE_HASH_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve_hash.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -51,6 +52,10 @@ SOLVE_TREE_MAX_EMPTIES = 16  # include/othello_solve_tree.h
 SOLVE_TREE_NOROOM = 4
 SOLVE_TREE_MIN_NODES = 64
 SOLVE_TREE_DEFAULT_NODES = 65536
+SOLVE_HASH_MIN_BITS, SOLVE_HASH_MAX_BITS = 4, 26  # include/othello_solve_hash.h
+SOLVE_HASH_ENTRY_BYTES = 32
+SOLVE_HASH_MIN_EMPTIES_LO, SOLVE_HASH_MIN_EMPTIES_HI = 1, 12
+SOLVE_HASH_DEFAULT_MIN_EMPTIES = 8
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -141,6 +146,14 @@ SOLVE_TREE_SIGNATURES = {
     "othe_solve_grid": (_I, [_I64]),
 }
 
+# the split solver with a transposition table, include/othello_solve_hash.h (its own prefix likewise):
+# othe_solve's arguments with hash_bits, hash_min_empties, table, table_bytes in front of the stream
+SOLVE_HASH_SIGNATURES = {
+    "othh_solve_hashed": (_I, [_P, _P, _I, _I, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _I64, ctypes.c_int32, _P, _I64,
+                               _I, _I, _P, _I64, _P]),
+    "othh_hash_bytes": (_I64, [_I]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -172,7 +185,8 @@ def load():
     except OSError as e:
         raise OthelloLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES, **PLAY_SIGNATURES,
-                              **TREE_SIGNATURES, **ORDER_SIGNATURES, **SOLVE_TREE_SIGNATURES}.items():
+                              **TREE_SIGNATURES, **ORDER_SIGNATURES, **SOLVE_TREE_SIGNATURES,
+                              **SOLVE_HASH_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -15,6 +15,9 @@
 //      the position's answer.
 // With order = 1 the third launch is split_solve_tasks_ordered: the same loop
 // around solve_order_core.hpp's advance_ordered().
+// With a transposition table (include/othello_solve_hash.h) the
+// third launch is split_solve_tasks_hashed<ordered>: the same loop around
+// solve_hash_core.hpp's machines, which probe and store in the caller's table.
 //
 // What one block writes and another reads inside the task launch is the state
 // word of a node and the position's node counter, both touched by agent-scope
@@ -22,8 +25,10 @@
 // waits for another: every loop is bounded by the tree's height, by the
 // children of one node or by node_limit.
 #include "../../include/othello_solve.h"
+#include "../../include/othello_solve_hash.h"
 #include "../../include/othello_solve_tree.h"
 #include "device_common.hpp"
+#include "solve_hash_core.hpp"
 #include "solve_order_core.hpp"
 #include "solve_tree_core.hpp"
 
@@ -32,6 +37,10 @@ static_assert(OTHE_MAX_EMPTIES == othe::kMaxEmpties && OTHE_NOROOM == othe::kNoR
               "header and core disagree");
 static_assert(OTHS_SKIPPED == oths::kSkipped && OTHS_SOLVED == oths::kSolved && OTHS_INVALID == oths::kInvalid &&
                   OTHS_LIMIT == oths::kLimit && OTHS_NO_MOVE == oths::kNoMove && OTH_PASS == oths::kPassMove,
+              "header and core disagree");
+static_assert(OTHH_MIN_BITS == othh::kMinBits && OTHH_MAX_BITS == othh::kMaxBits &&
+                  OTHH_MIN_EMPTIES_LO == othh::kMinGate && OTHH_MIN_EMPTIES_HI == othh::kMaxGate &&
+                  OTHH_DEFAULT_MIN_EMPTIES == othh::kDefaultGate && OTHH_ENTRY_BYTES == othh::kEntryBytes,
               "header and core disagree");
 
 namespace {
@@ -420,17 +429,142 @@ __global__ __launch_bounds__(kTaskBlock) void split_solve_tasks_ordered(TaskArgs
     }
 }
 
-// one cache for split_solve_tasks (order 0), one for the ordered kernel (1)
-othd::ResidentBlocks g_resident[2];
+// ------------------------------------------------------------------ tasks with the table
+// solve_hash_core.hpp's atomics policy on the device.  Every word of the table
+// is read and written by agent-scope atomics on global (address space 1)
+// pointers: they bypass the CU's L1, which another CU's stores never refresh,
+// and reach the memory all XCDs share.  The orderings are agent-scope fences
+// around relaxed accesses.
+struct DeviceHashAtomics {
+    typedef __attribute__((address_space(1))) unsigned long long gu64;
+    static __device__ __forceinline__ gu64* g(u64* p) { return (gu64*)(p); }
+    static __device__ __forceinline__ u64 load(u64* p) {
+        return __hip_atomic_load(g(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    static __device__ __forceinline__ u64 seq_load(u64* p) { return load(p); }   // read_fence() makes it an acquire
+    static __device__ __forceinline__ u64 data_load(u64* p) { return load(p); }  // read_fence() keeps seq's second load behind it
+    static __device__ __forceinline__ void read_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); }
+    static __device__ __forceinline__ bool claim(u64* p, u64 expected, u64 desired) {
+        unsigned long long e = expected;
+        const bool won = __hip_atomic_compare_exchange_strong(g(p), &e, (unsigned long long)desired, __ATOMIC_RELAXED,
+                                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // acquire: the earlier writers' words; release: the claim before this writer's words
+        if (won) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
+        return won;
+    }
+    static __device__ __forceinline__ void data_store(u64* p, u64 v) {
+        __hip_atomic_store(g(p), (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    static __device__ __forceinline__ void publish(u64* p, u64 v) {
+        __hip_atomic_store(g(p), (unsigned long long)v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
+};
 
-int resident_blocks(int order) {
-    const void* kernel = order ? reinterpret_cast<const void*>(split_solve_tasks_ordered)
-                               : reinterpret_cast<const void*>(split_solve_tasks);
-    return g_resident[order].get(kernel, kTaskBlock);
+// split_solve_tasks' and split_solve_tasks_ordered's persistent loop, the
+// refill protocol and the fold unchanged, around solve_hash_core.hpp's
+// machines.  One body for both orders: these kernels have no earlier code to
+// keep.
+template <bool kOrdered>
+__global__ __launch_bounds__(kTaskBlock) void split_solve_tasks_hashed(TaskArgs a, othh::Table tab) {
+    __shared__ u32 frames[oths::kFrames * oths::kFields * kTaskBlock];
+    const u32 lane = threadIdx.x;
+    const u64 ntasks = a.s.tbase[a.n];
+    const u64 total = ntasks + a.lanes;
+    LdsStack stk{frames + lane};
+    oths::Lane L;
+    L.depth = -1;
+    othm::Order Q;
+    othm::order_reset(Q);
+    u64 pos = 0;
+    u32 node = 0;
+    bool exhausted = false;  // the lane has made its failing request
+    for (;;) {
+        const bool idle = L.depth < 0;
+        const bool want = idle && !exhausted;
+        const u64 wantm = __ballot(want);
+        const u64 busym = __ballot(!idle);
+        if ((wantm | busym) == 0) break;
+        const u64 cnt = (u64)__popcll(wantm);
+        bool done = false;  // the lane's task ended in this turn of the loop
+        int v = 0;
+        u64 lim = 0;
+        u32 spent = 0;
+        if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
+            u64 base = 0;
+            if (lane == 0) {
+                base = atomicAdd(a.work, cnt);
+                if (base + cnt == total) atomicExch(a.work, 0ull);  // every request is made: reset
+            }
+            base = __shfl(base, 0);
+            if (want) {
+                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
+                if (g >= ntasks) {
+                    exhausted = true;
+                } else {
+                    u64 lo = 0, hi = a.n;  // the last position whose first task is <= g
+                    while (hi - lo > 1) {
+                        const u64 mid = (lo + hi) >> 1;
+                        if (a.s.tbase[mid] <= g) lo = mid; else hi = mid;
+                    }
+                    pos = lo;
+                    node = a.s.tasks[pos * a.npp + (g - a.s.tbase[pos])];
+                    Node* slab = a.s.nodes + pos * a.npp;
+                    int alpha, beta;
+                    othe::window<DeviceAtomics>(slab, node, kShareBounds, alpha, beta);
+                    if (alpha >= beta) {  // cut off before it began: it reports its beta
+                        done = true;
+                        v = beta;
+                    } else {
+                        othe::start_task(L, slab[node], alpha, beta);
+                        othm::order_reset(Q);
+                    }
+                }
+            }
+        }
+        if (L.depth >= 0) {
+            if constexpr (kOrdered)
+                othh::advance_ordered_hashed<DeviceRules, DeviceHashAtomics>(L, Q, stk, tab, a.limit);
+            else
+                othh::advance_hashed<DeviceRules, DeviceHashAtomics>(L, stk, tab, a.limit);
+            if (L.depth < 0) {
+                done = true;
+                v = L.value;
+                lim = L.status == oths::kLimit ? othe::kLimitBit : 0ull;
+                spent = L.nodes;
+            }
+        }
+        if (done) {
+            Node* slab = a.s.nodes + pos * a.npp;
+            PosHdr* hdr = a.s.hdr + pos;
+            const u64 before = __hip_atomic_fetch_add(&hdr->nodes, (unsigned long long)spent, __ATOMIC_RELAXED,
+                                                      __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("" ::"v"(before) : "memory");
+            if (othe::fold_up<DeviceAtomics>(slab, node, v, lim)) {
+                int value;
+                u32 mv, st;
+                othe::root_result<DeviceAtomics>(slab, value, mv, st);
+                emit(a.out, pos, value, mv, st,
+                     __hip_atomic_load(&hdr->nodes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            }
+        }
+    }
 }
 
-int task_grid(int64_t tasks, int order) {
-    const int resident = resident_blocks(order);
+// one cache for split_solve_tasks (order 0), one for the ordered kernel (1),
+// two for their hashed twins
+othd::ResidentBlocks g_resident[4];
+
+int resident_blocks(int order, bool hashed) {
+    const void* kernel =
+        hashed ? (order ? reinterpret_cast<const void*>(split_solve_tasks_hashed<true>)
+                        : reinterpret_cast<const void*>(split_solve_tasks_hashed<false>))
+               : (order ? reinterpret_cast<const void*>(split_solve_tasks_ordered)
+                        : reinterpret_cast<const void*>(split_solve_tasks));
+    return g_resident[order + (hashed ? 2 : 0)].get(kernel, kTaskBlock);
+}
+
+int task_grid(int64_t tasks, int order, bool hashed = false) {
+    const int resident = resident_blocks(order, hashed);
     if (resident <= 0) return -1;
     const int cap = std::min(std::max(env_int("OTH_SOLVE_BLOCKS", resident), 1), resident);
     return (int)std::min<int64_t>(std::max<int64_t>((tasks + kTaskBlock - 1) / kTaskBlock, 1), (int64_t)cap);
@@ -443,19 +577,11 @@ int64_t slab_nodes(int64_t n, int64_t npp) {
     return n * npp;
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t othe_scratch_bytes(int64_t n, int32_t nodes_per_position) {
-    if (slab_nodes(n, nodes_per_position) < 0) return OTH_EINVAL;
-    return scratch_layout(n, nodes_per_position, nullptr, nullptr);
-}
-
-int othe_solve(const uint64_t* boards, const uint8_t* turn, int max_empties, int task_empties, int order,
-               uint32_t node_limit, int8_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes,
-               void* scratch, int64_t scratch_bytes, int32_t nodes_per_position, uint64_t* work, int64_t n,
-               void* stream) {
+// othe_solve's launches; with a table the task launch is the hashed kernel's
+int launch_solve(const uint64_t* boards, const uint8_t* turn, int max_empties, int task_empties, int order,
+                 uint32_t node_limit, int8_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes, void* scratch,
+                 int64_t scratch_bytes, int32_t nodes_per_position, uint64_t* work, int64_t n, const othh::Table* tab,
+                 void* stream) {
     if (order < 0 || order > 1) return OTH_EINVAL;
     if (n < 0 || n > 0x7FFFFFFF || !work || (n > 0 && !boards)) return OTH_EINVAL;
     if (max_empties < 0 || max_empties > OTHE_MAX_EMPTIES || task_empties < 1 || task_empties > OTHS_MAX_EMPTIES)
@@ -466,7 +592,7 @@ int othe_solve(const uint64_t* boards, const uint8_t* turn, int max_empties, int
     if (!scratch || ((uintptr_t)scratch & 7) || scratch_bytes < scratch_layout(n, nodes_per_position, nullptr, nullptr))
         return OTH_EINVAL;
     // a position has no more tasks than its slab holds
-    const int grid = task_grid(total_nodes, order);
+    const int grid = task_grid(total_nodes, order, tab != nullptr);
     if (grid <= 0) return status_of(hipErrorInvalidDevice);
     hipStream_t st = (hipStream_t)stream;
     Outputs out{value, best_move, status, nodes};
@@ -492,11 +618,54 @@ int othe_solve(const uint64_t* boards, const uint8_t* turn, int max_empties, int
     t.lanes = (u64)grid * kTaskBlock;
     t.npp = (u32)nodes_per_position;
     t.limit = node_limit ? node_limit : OTHS_DEFAULT_NODE_LIMIT;
-    if (order)
+    if (tab && order)
+        split_solve_tasks_hashed<true><<<(unsigned)grid, kTaskBlock, 0, st>>>(t, *tab);
+    else if (tab)
+        split_solve_tasks_hashed<false><<<(unsigned)grid, kTaskBlock, 0, st>>>(t, *tab);
+    else if (order)
         split_solve_tasks_ordered<<<(unsigned)grid, kTaskBlock, 0, st>>>(t);
     else
         split_solve_tasks<<<(unsigned)grid, kTaskBlock, 0, st>>>(t);
     return status_of(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t othe_scratch_bytes(int64_t n, int32_t nodes_per_position) {
+    if (slab_nodes(n, nodes_per_position) < 0) return OTH_EINVAL;
+    return scratch_layout(n, nodes_per_position, nullptr, nullptr);
+}
+
+int othe_solve(const uint64_t* boards, const uint8_t* turn, int max_empties, int task_empties, int order,
+               uint32_t node_limit, int8_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes,
+               void* scratch, int64_t scratch_bytes, int32_t nodes_per_position, uint64_t* work, int64_t n,
+               void* stream) {
+    return launch_solve(boards, turn, max_empties, task_empties, order, node_limit, value, best_move, status, nodes,
+                        scratch, scratch_bytes, nodes_per_position, work, n, nullptr, stream);
+}
+
+int64_t othh_hash_bytes(int hash_bits) {
+    if (hash_bits < OTHH_MIN_BITS || hash_bits > OTHH_MAX_BITS) return OTH_EINVAL;
+    return (int64_t)OTHH_ENTRY_BYTES << hash_bits;
+}
+
+int othh_solve_hashed(const uint64_t* boards, const uint8_t* turn, int max_empties, int task_empties, int order,
+                      uint32_t node_limit, int8_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes,
+                      void* scratch, int64_t scratch_bytes, int32_t nodes_per_position, uint64_t* work, int64_t n,
+                      int hash_bits, int hash_min_empties, void* table, int64_t table_bytes, void* stream) {
+    if (hash_bits < OTHH_MIN_BITS || hash_bits > OTHH_MAX_BITS || hash_min_empties < OTHH_MIN_EMPTIES_LO ||
+        hash_min_empties > OTHH_MIN_EMPTIES_HI)
+        return OTH_EINVAL;
+    if (!table || ((uintptr_t)table & (OTHH_ENTRY_BYTES - 1)) || table_bytes < othh_hash_bytes(hash_bits))
+        return OTH_EINVAL;
+    othh::Table tab;
+    tab.e = static_cast<othh::Entry*>(table);
+    tab.shift = 64 - hash_bits;
+    tab.min_empties = hash_min_empties;
+    return launch_solve(boards, turn, max_empties, task_empties, order, node_limit, value, best_move, status, nodes,
+                        scratch, scratch_bytes, nodes_per_position, work, n, &tab, stream);
 }
 
 int othe_solve_grid(int64_t tasks) {

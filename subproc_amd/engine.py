@@ -34,7 +34,11 @@ move is the exact solver's (ops.solve: best final disc difference, ties to the
 lowest square), whatever the policy.  ``--solve-task-empties T`` (T = 1..12)
 makes that solve the split solver (ops.solve(task_empties=T), the position's
 tree spread over the whole device) and lets K go to 16; ``--solve-order 1``
-orders the moves inside its tasks (default: ``--order``'s value).
+orders the moves inside its tasks (default: ``--order``'s value);
+``--solve-hash-bits B`` (B = 4..26, needs ``--solve-task-empties``) gives the
+tasks a transposition table of 2**B entries (ops.SolveTable) that the engine
+keeps for its life, so successive ``go``s of one endgame reuse what the earlier
+ones solved: the same moves.
 ``--policy search --depth D`` (D = 1..8) looks D plies ahead: the move is
 ops.search's, a fixed-depth alpha-beta with the eval table at the horizon (one
 launch per ``go``; depth 1 is the "eval" policy's move).  ``--solve-empties``
@@ -58,7 +62,7 @@ from .codec import handstr_from_coord
 
 class Engine:
     def __init__(self, name="GPU", policy="greedy", seed=0, weights=None, solve_empties=0, depth=1, split=0, order=0,
-                 solve_task_empties=None, solve_order=None):
+                 solve_task_empties=None, solve_order=None, solve_hash_bits=None):
         top = _lib.SOLVE_MAX_EMPTIES if solve_task_empties is None else _lib.SOLVE_TREE_MAX_EMPTIES
         if not 0 <= solve_empties <= top:
             raise ValueError(f"solve_empties must lie in 0..{top}" + (
@@ -68,6 +72,11 @@ class Engine:
             raise ValueError(f"solve_task_empties must lie in 1..{_lib.SOLVE_MAX_EMPTIES}")
         if solve_order is not None and solve_order not in (0, 1):
             raise ValueError("solve_order must be 0 or 1")
+        if solve_hash_bits is not None:
+            if solve_task_empties is None:
+                raise ValueError("solve_hash_bits needs solve_task_empties: the table serves the split solver's tasks")
+            if not _lib.SOLVE_HASH_MIN_BITS <= solve_hash_bits <= _lib.SOLVE_HASH_MAX_BITS:
+                raise ValueError(f"solve_hash_bits must lie in {_lib.SOLVE_HASH_MIN_BITS}..{_lib.SOLVE_HASH_MAX_BITS}")
         if not 0 <= split <= _lib.TREE_MAX_SPLIT:
             raise ValueError(f"split must lie in 0..{_lib.TREE_MAX_SPLIT}")
         if not 1 <= depth <= _lib.SEARCH_MAX_DEPTH + split:
@@ -78,6 +87,8 @@ class Engine:
         self.solve_task_empties = solve_task_empties
         # (the solver's tasks take the search's --order unless --solve-order says otherwise)
         self.solve_order = (order if solve_order is None else solve_order) if solve_task_empties is not None else 0
+        self.solve_hash_bits = solve_hash_bits
+        self._solve_table = None  # made on the first solve, kept for the engine's life, never cleared
         self.order = order
         self.depth = depth
         # (a depth the split leaves no plies below is searched unsplit)
@@ -129,8 +140,10 @@ class Engine:
         side = torch.full((1,), b.turn, dtype=torch.uint8, device=dev)
         # (a position that would need more than 2**24 nodes -- none at <= 12
         # empties in DESIGN.md §12's samples -- falls back to the policy)
+        if self.solve_hash_bits is not None and self._solve_table is None:
+            self._solve_table = ops.SolveTable(self.solve_hash_bits, dev)
         r = ops.solve(boards, side, max_empties=self.solve_empties, node_limit=1 << 24,
-                      task_empties=self.solve_task_empties, order=self.solve_order)
+                      task_empties=self.solve_task_empties, order=self.solve_order, table=self._solve_table)
         sq = int(r.best_move.cpu()[0])
         if int(r.status.cpu()[0]) != _lib.SOLVE_SOLVED or sq > 63:
             return None
@@ -193,7 +206,8 @@ class Engine:
                 extra += " solve_empties=%d" % self.solve_empties
                 if self.solve_task_empties is not None:
                     extra += " solve_task_empties=%d" % self.solve_task_empties + (
-                        " solve_order=%d" % self.solve_order if self.solve_order > 0 else "")
+                        " solve_order=%d" % self.solve_order if self.solve_order > 0 else "") + (
+                        " solve_hash_bits=%d" % self.solve_hash_bits if self.solve_hash_bits is not None else "")
             out("%s policy=%s%s" % (self.name, self.policy, extra))
         elif cmd == "verbose 1":
             b = self.board
@@ -241,10 +255,15 @@ def main(argv=None):
                    help="spread the exact solver's tree over the device: nodes of at most T empties become tasks (1..12)")
     p.add_argument("--solve-order", type=int, choices=[0, 1], default=None,
                    help="move ordering inside the split solver's tasks (default: --order's value)")
+    p.add_argument("--solve-hash-bits", type=int, default=None, metavar="B",
+                   help="give the split solver's tasks a transposition table of 2**B entries, kept between moves "
+                        "(4..26; needs --solve-task-empties)")
     a = p.parse_args(argv)
+    if a.solve_hash_bits is not None and a.solve_task_empties is None:
+        p.error("--solve-hash-bits needs --solve-task-empties")
     weights = params.read_paramgen(a.params)[1] if a.params else None
     eng = Engine(a.name, a.policy, a.seed, weights, a.solve_empties, a.depth, a.split, a.order,
-                 a.solve_task_empties, a.solve_order)
+                 a.solve_task_empties, a.solve_order, a.solve_hash_bits)
 
     def out(s):
         sys.stdout.write(s + "\n")

@@ -63,14 +63,18 @@ class VecEnv:
         return ops.result(self.boards).terminal.bool()
 
     def solve(self, max_empties=12, node_limit=0, task_empties=None, order=0,
-              nodes_per_position=_lib.SOLVE_TREE_DEFAULT_NODES):
+              nodes_per_position=_lib.SOLVE_TREE_DEFAULT_NODES, table=None,
+              hash_min_empties=_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES):
         """Exact endgame solve of the current state (ops.solve): per game the
         disc difference under perfect play from the mover's side and the move
         that achieves it, for the games with at most `max_empties` empties.
         `task_empties` = T: the split solver, for a few games at a time and up
-        to 16 empties; `order` = 1 orders the moves inside its tasks."""
+        to 16 empties; `order` = 1 orders the moves inside its tasks; `table`
+        (an ops.SolveTable, kept by the caller) gives them a transposition
+        table, `hash_min_empties` its gate: the same answers."""
         return ops.solve(self.boards, self.turn, max_empties=max_empties, node_limit=node_limit,
-                         task_empties=task_empties, order=order, nodes_per_position=nodes_per_position)
+                         task_empties=task_empties, order=order, nodes_per_position=nodes_per_position, table=table,
+                         hash_min_empties=hash_min_empties)
 
     def search(self, depth, weights=None, node_limit=0, split=0, order=0):
         """Depth-limited search of the current state (ops.search): per game the

@@ -413,8 +413,33 @@ def rollout_runner(n, seed, game_id0=0, policy="eval", weights_a=None, weights_b
 SolveResult = namedtuple("SolveResult", "value best_move status nodes")
 
 
+class SolveTable:
+    """The split solver's transposition table (include/othello_solve_hash.h):
+    2**bits entries of 32 bytes in device memory, zeroed (all zero is empty).
+    The solver never clears it: what one ``ops.solve(..., table=t)`` proved is
+    there for the next, whatever its order, task_empties or batch.  ``data`` is
+    the int64 tensor, ``nbytes`` its size, ``clear()`` empties it.  One table
+    serves the calls of one stream, one after the other."""
+
+    def __init__(self, bits, device="cuda"):
+        bits = int(bits)
+        if not _lib.SOLVE_HASH_MIN_BITS <= bits <= _lib.SOLVE_HASH_MAX_BITS:
+            raise ValueError(f"bits must lie in {_lib.SOLVE_HASH_MIN_BITS}..{_lib.SOLVE_HASH_MAX_BITS}")
+        self.bits = bits
+        self.nbytes = _lib.SOLVE_HASH_ENTRY_BYTES << bits
+        self.data = torch.zeros(self.nbytes // 8, dtype=torch.int64, device=device)
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def clear(self):
+        self.data.zero_()
+
+
 def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=None, task_empties=None, order=0,
-          nodes_per_position=_lib.SOLVE_TREE_DEFAULT_NODES):
+          nodes_per_position=_lib.SOLVE_TREE_DEFAULT_NODES, table=None,
+          hash_min_empties=_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES):
     """Exact endgame solve (oths_solve, include/othello_solve.h): for every
     position with at most ``max_empties`` (0..12) empty squares, the final disc
     difference under perfect play by both sides, from the mover's side (White
@@ -449,6 +474,14 @@ def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=Non
     none of them ends as NOROOM.  The scratch (othe_scratch_bytes) is allocated
     here, so this form does not run under graph capture.  Without
     ``task_empties`` the call is oths_solve's, and ``order`` must be 0.
+
+    ``table`` (a :class:`SolveTable`; needs ``task_empties``) gives the tasks a
+    transposition table (othh_solve_hashed, include/othello_solve_hash.h):
+    search frames with at least ``hash_min_empties`` (1..12) empties look their
+    position up and store what they prove.  Values, moves and statuses are the
+    same with any table, of any size and contents, and any ``hash_min_empties``
+    (only a position within reach of ``node_limit`` may end differently): both
+    are speed knobs.  Keep the table between calls to reuse what was solved.
     """
     n = _n(boards)
     capturing = torch.cuda.is_current_stream_capturing()
@@ -457,9 +490,19 @@ def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=Non
                            "tensor zeroed before the capture, one per captured launch")
     if not 0 <= int(node_limit) < 2**32:
         raise ValueError("node_limit must fit 32 bits")
+    if table is not None:
+        if task_empties is None:
+            raise ValueError("ops.solve's table serves the split solver's tasks: table needs task_empties")
+        if not isinstance(table, SolveTable):
+            raise TypeError("table must be an ops.SolveTable")
+        if not _lib.SOLVE_HASH_MIN_EMPTIES_LO <= int(hash_min_empties) <= _lib.SOLVE_HASH_MIN_EMPTIES_HI:
+            raise ValueError(f"hash_min_empties must lie in {_lib.SOLVE_HASH_MIN_EMPTIES_LO}.."
+                             f"{_lib.SOLVE_HASH_MIN_EMPTIES_HI}")
+        if table.device != boards.device:
+            raise ValueError(f"table is on {table.device}, boards on {boards.device}")
     if task_empties is not None:
         return _solve_split(boards, turn, n, int(max_empties), int(task_empties), int(order), int(node_limit),
-                            want_nodes, work, int(nodes_per_position), capturing)
+                            want_nodes, work, int(nodes_per_position), capturing, table, int(hash_min_empties))
     if int(order) != 0:
         raise ValueError("ops.solve orders moves only inside the split solver's tasks: order needs task_empties")
     d = boards.device
@@ -484,8 +527,9 @@ def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=Non
 
 
 def _solve_split(boards, turn, n, max_empties, task_empties, order, node_limit, want_nodes, work, nodes_per_position,
-                 capturing):
-    """:func:`solve` with task_empties set: othe_solve on a scratch of its own."""
+                 capturing, table=None, hash_min_empties=_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES):
+    """:func:`solve` with task_empties set: othe_solve on a scratch of its own
+    (othh_solve_hashed with a table)."""
     if capturing:
         raise RuntimeError("ops.solve(task_empties=...) allocates its scratch and does not run under graph capture")
     if not -2**31 <= nodes_per_position < 2**31:
@@ -505,15 +549,22 @@ def _solve_split(boards, turn, n, max_empties, task_empties, order, node_limit, 
     w = work_word(d) if work is None else work
     pw = _dev(w, "work", torch.int64, (1,), d)
     with torch.cuda.device(d):
-        rc = lib.othe_solve(pb, pt, max_empties, task_empties, order, node_limit, val.data_ptr(), mv.data_ptr(),
-                            st.data_ptr(), None if nd is None else nd.data_ptr(), scratch.data_ptr(),
-                            scratch.numel() * 8, nodes_per_position, pw, n, _stream())
+        args = (pb, pt, max_empties, task_empties, order, node_limit, val.data_ptr(), mv.data_ptr(), st.data_ptr(),
+                None if nd is None else nd.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, nodes_per_position,
+                pw, n)
+        if table is None:
+            what = "othe_solve"
+            rc = lib.othe_solve(*args, _stream())
+        else:
+            what = "othh_solve_hashed"
+            rc = lib.othh_solve_hashed(*args, table.bits, hash_min_empties, table.data.data_ptr(), table.nbytes,
+                                       _stream())
         if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
             if work is None:
                 _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
             else:
                 w.zero_()
-        check(rc, "othe_solve")
+        check(rc, what)
     # (the caching allocator hands the scratch to later work of THIS stream only)
     return SolveResult(val, mv, st, nd)
 
@@ -844,7 +895,8 @@ def from_numpy_u64(a, device="cuda"):
     return torch.from_numpy(a.view(np.int64).copy()).to(device)
 
 
-__all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", "solve", "search", "play", "sample_midgame",
+__all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", "solve", "SolveTable", "search", "play",
+           "sample_midgame",
            "replay",
            "book_text", "features", "evaluate", "to_numpy_u64", "from_numpy_u64",
            "StepResult", "Result", "RolloutResult", "PlayResult", "Positions", "Replay", "BLACK", "WHITE", "PASS", "HIST_BINS"]

@@ -9,7 +9,10 @@ worst wall time of a launch (host clock around the call and a synchronise,
 after one warm-up launch per method on the first position), the nodes of all
 launches (under a split they depend on timing), the statuses, library_sha16.
 Methods: "lane" (E <= 12), "search" (E <= 12), "T<t>o<o>" for every t of
---task-empties and o of --order.  Every launch carries --node-limit (per
+--task-empties and o of --order, and with --hash-bits "T<t>o<o>h<bits>g<gate>f"
+(ops.solve(..., table=) on a table emptied before every launch, outside the
+timed region) and "...k" (one table kept across the launches of the line) for
+every gate of --hash-min-empties.  Every launch carries --node-limit (per
 position for "lane", per task otherwise); a method stops early once it has used
 --budget-s seconds and says how many launches it timed.  Nothing raises a
 limit silently: a position that ends as LIMIT or NOROOM is counted in
@@ -31,6 +34,18 @@ import torch  # noqa: E402
 from subproc_amd import _lib  # noqa: E402
 
 
+def hashed_method(ops, a, e, te, o, bits, gate, kept):
+    """ops.solve with a table of its own; the caller clears it between launches unless it is kept."""
+    table = ops.SolveTable(bits, "cuda")
+
+    def fn(bb, tt):
+        return ops.solve(bb, tt, max_empties=e, node_limit=a.node_limit, want_nodes=True, task_empties=te, order=o,
+                         nodes_per_position=a.nodes_per_position, table=table, hash_min_empties=gate)
+
+    fn.table, fn.kept = table, kept
+    return fn
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     p.add_argument("--empties", type=int, nargs="+", default=[10, 12, 14, 16])
@@ -43,15 +58,18 @@ def main():
     p.add_argument("--nodes-per-position", type=int, default=_lib.SOLVE_TREE_DEFAULT_NODES)
     p.add_argument("--budget-s", type=float, default=20.0)
     p.add_argument("--tag", default="", help="recorded on every line")
-    p.add_argument("--lib", default=None, help="another build of the library (the parent commit's, for lane and search)")
+    p.add_argument("--hash-bits", type=int, nargs="*", default=[], help="also time the split solver with a table of 2**B entries")
+    p.add_argument("--hash-min-empties", type=int, nargs="+", default=[_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES])
+    p.add_argument("--no-plain", action="store_true", help="skip the split lines without a table")
+    p.add_argument("--lib", default=None, help="another build of the library (the parent commit's: no table lines)")
     a = p.parse_args()
     if a.node_limit <= 0:
         p.error("every launch carries a node limit")
     if a.lib:
         _lib.LIB_PATH = os.path.abspath(a.lib)
-        _lib.SOLVE_TREE_SIGNATURES = {}  # (a build from before this set has nothing to bind it to)
-        if "split" in a.methods:
-            p.error("--lib measures the methods the other build has: --methods lane search")
+        _lib.SOLVE_HASH_SIGNATURES = {}  # (a build from before this set has nothing to bind it to)
+        if a.hash_bits:
+            p.error("--lib measures the methods the other build has: no --hash-bits")
     import solve_cases
     from subproc_amd import ops
 
@@ -71,16 +89,27 @@ def main():
         if "split" in a.methods:
             for te in a.task_empties:
                 for o in a.order:
-                    methods.append(("T%do%d" % (te, o), lambda bb, tt, te=te, o=o: ops.solve(
-                        bb, tt, max_empties=e, node_limit=a.node_limit, want_nodes=True, task_empties=te, order=o,
-                        nodes_per_position=a.nodes_per_position)))
+                    if not a.no_plain:
+                        methods.append(("T%do%d" % (te, o), lambda bb, tt, te=te, o=o: ops.solve(
+                            bb, tt, max_empties=e, node_limit=a.node_limit, want_nodes=True, task_empties=te, order=o,
+                            nodes_per_position=a.nodes_per_position)))
+                    for bits in a.hash_bits:
+                        for gate in a.hash_min_empties:
+                            for kept in (False, True):
+                                methods.append(("T%do%dh%dg%d%s" % (te, o, bits, gate, "k" if kept else "f"),
+                                                hashed_method(ops, a, e, te, o, bits, gate, kept)))
         launches = [(i, i + a.batch) for i in range(0, k - a.batch + 1, a.batch)]
         for name, fn in methods:
             fn(boards[:1], turn[:1])  # warm-up
             torch.cuda.synchronize()
+            if hasattr(fn, "table"):
+                fn.table.clear()
             ms, nodes, status, unsolved = [], 0, {}, []
             t_start = time.perf_counter()
             for lo, hi in launches:
+                if hasattr(fn, "table") and not fn.kept:
+                    fn.table.clear()
+                    torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 r = fn(boards[lo:hi], turn[lo:hi])
                 torch.cuda.synchronize()
