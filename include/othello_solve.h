@@ -43,6 +43,8 @@ extern "C" {
 #define OTHS_SOLVED 1
 #define OTHS_INVALID 2 /* black & white overlap: value 0, best_move 255, nodes 0 */
 #define OTHS_LIMIT 3   /* node_limit reached: value and best_move are 0 / 255 */
+/* 4 is OTHE_NOROOM (othello_solve_tree.h) */
+#define OTHS_BADWINDOW 5 /* othello_solve_window.h: the position's window is out of range or empty */
 #define OTHS_NO_MOVE 255
 #define OTHS_DEFAULT_NODE_LIMIT (1u << 28)
 

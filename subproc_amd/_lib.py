@@ -16,6 +16,7 @@ TREE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_tree.h")
 ORDER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_order.h")
 SOLVE_TREE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve_tree.h")
 SOLVE_HASH_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve_hash.h")
+SOLVE_WINDOW_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve_window.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -56,6 +57,8 @@ SOLVE_HASH_MIN_BITS, SOLVE_HASH_MAX_BITS = 4, 26  # include/othello_solve_hash.h
 SOLVE_HASH_ENTRY_BYTES = 32
 SOLVE_HASH_MIN_EMPTIES_LO, SOLVE_HASH_MIN_EMPTIES_HI = 1, 12
 SOLVE_HASH_DEFAULT_MIN_EMPTIES = 8
+SOLVE_BADWINDOW = 5          # include/othello_solve.h, set by the calls of include/othello_solve_window.h
+SOLVE_ALPHA_MIN, SOLVE_BETA_MAX = -65, 65
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -154,6 +157,14 @@ SOLVE_HASH_SIGNATURES = {
     "othh_hash_bytes": (_I64, [_I]),
 }
 
+# the exact solvers with a root window, include/othello_solve_window.h (its own prefix likewise): oths_solve's
+# arguments with alpha, beta after turn; othh_solve_hashed's with alpha, beta in front of hash_bits
+SOLVE_WINDOW_SIGNATURES = {
+    "othw_solve": (_I, [_P, _P, _P, _P, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _I64, _P]),
+    "othw_solve_split": (_I, [_P, _P, _I, _I, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _I64, ctypes.c_int32, _P, _I64,
+                              _P, _P, _I, _I, _P, _I64, _P]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -186,7 +197,7 @@ def load():
         raise OthelloLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES, **PLAY_SIGNATURES,
                               **TREE_SIGNATURES, **ORDER_SIGNATURES, **SOLVE_TREE_SIGNATURES,
-                              **SOLVE_HASH_SIGNATURES}.items():
+                              **SOLVE_HASH_SIGNATURES, **SOLVE_WINDOW_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

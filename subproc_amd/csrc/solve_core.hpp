@@ -29,6 +29,11 @@
 // it only when strictly greater.  The root starts at (-65, 65), so every root
 // move's first equal-or-better rival fails low and the move kept is the LOWEST
 // square among the maximisers (moves are taken lowest bit first everywhere).
+// start() may be given a narrower root window (alpha, beta): the same machine
+// then keeps the lowest square among the moves that reach beta when the value
+// does, and no move (kNoMove) when no move beats alpha.  A finished game is
+// scored as it is, whatever the window, so a root's value is clamped into its
+// window by whoever emits it (clamp_to_window).
 //
 // Nodes = MOVE steps (placements) + passes.  A position whose next node would
 // exceed `limit` ends as kLimit; every step pops a frame or makes a node (or
@@ -55,6 +60,8 @@ constexpr int kFrames = kMaxEmpties - 1;
 constexpr int kFields = 7;                // 32-bit words per frame: P, O, M (2 each), packed window + flags
 
 constexpr u32 kSkipped = 0, kSolved = 1, kInvalid = 2, kLimit = 3;  // OTHS_SKIPPED ..
+constexpr u32 kBadWindow = 5;             // OTHS_BADWINDOW (4 is the split solver's OTHE_NOROOM)
+constexpr int kInf = 65;                  // the full root window is (-kInf, kInf)
 constexpr u32 kNoMove = 255, kPassMove = 64;
 
 constexpr u32 kFresh = 1;   // the frame never had a move and its pass is not checked yet
@@ -79,13 +86,14 @@ OTHS_FN u32 pack(int alpha, int beta, u32 flags) {
 }
 
 // a position for the search: mover's discs P, opponent's O (disjoint, at most
-// kMaxEmpties empty squares: the caller has checked both)
-OTHS_FN void start(Lane& L, u64 P, u64 O) {
+// kMaxEmpties empty squares: the caller has checked both) and the root window
+// -kInf <= alpha < beta <= kInf (window_ok: the caller has checked that too)
+OTHS_FN void start(Lane& L, u64 P, u64 O, int alpha = -kInf, int beta = kInf) {
     L.P = P;
     L.O = O;
     L.M = 0;
-    L.alpha = -65;
-    L.beta = 65;
+    L.alpha = alpha;
+    L.beta = beta;
     L.flags = kRootNew;
     L.depth = 0;
     L.nodes = 0;
@@ -225,5 +233,12 @@ OTHS_FN u32 classify(u64 black, u64 white, int empties, int max_empties) {
     if (black & white) return kInvalid;
     return empties > max_empties ? kSkipped : kSolved;
 }
+
+
+OTHS_FN bool window_ok(int alpha, int beta) { return alpha >= -kInf && alpha < beta && beta <= kInf; }
+
+// a root's value as its caller sees it: the machine is fail-hard but for the
+// finished games, which are scored exactly
+OTHS_FN int clamp_to_window(int v, int alpha, int beta) { return v < alpha ? alpha : v > beta ? beta : v; }
 
 }  // namespace oths

@@ -18,6 +18,10 @@
 // With a transposition table (include/othello_solve_hash.h) the
 // third launch is split_solve_tasks_hashed<ordered>: the same loop around
 // solve_hash_core.hpp's machines, which probe and store in the caller's table.
+// With a root window (include/othello_solve_window.h) the
+// expansion keeps each position's window in its header and the third launch is
+// split_window_tasks<ordered, hashed>: the same loop, every task's window
+// derived under the root's own and the root's answer clamped into it.
 //
 // What one block writes and another reads inside the task launch is the state
 // word of a node and the position's node counter, both touched by agent-scope
@@ -27,6 +31,7 @@
 #include "../../include/othello_solve.h"
 #include "../../include/othello_solve_hash.h"
 #include "../../include/othello_solve_tree.h"
+#include "../../include/othello_solve_window.h"
 #include "device_common.hpp"
 #include "solve_hash_core.hpp"
 #include "solve_order_core.hpp"
@@ -41,6 +46,10 @@ static_assert(OTHS_SKIPPED == oths::kSkipped && OTHS_SOLVED == oths::kSolved && 
 static_assert(OTHH_MIN_BITS == othh::kMinBits && OTHH_MAX_BITS == othh::kMaxBits &&
                   OTHH_MIN_EMPTIES_LO == othh::kMinGate && OTHH_MIN_EMPTIES_HI == othh::kMaxGate &&
                   OTHH_DEFAULT_MIN_EMPTIES == othh::kDefaultGate && OTHH_ENTRY_BYTES == othh::kEntryBytes,
+              "header and core disagree");
+
+static_assert(OTHS_BADWINDOW == oths::kBadWindow && OTHW_ALPHA_MIN == -othe::kInf && OTHW_BETA_MAX == othe::kInf &&
+                  oths::kInf == othe::kInf,
               "header and core disagree");
 
 namespace {
@@ -67,7 +76,7 @@ static_assert(LdsStack::kFields == oths::kFields, "the frame's words");
 struct PosHdr {
     unsigned long long nodes;  // the expansion's, then + every task's (agent atomics in the task launch)
     u32 ntasks;
-    u32 pad;
+    u32 window;  // the root's (othe::pack_window), written by the expansion, read by split_window_tasks
 };
 
 // the caller's scratch, cut up: task prefix [n + 1], headers [n], task lists
@@ -118,6 +127,9 @@ struct ExpandArgs {
     u32 npp;
     int max_empties;
     int task_empties;
+    // each position's root window (othw_solve_split), NULL = -65 / 65 everywhere
+    const int8_t* alpha;
+    const int8_t* beta;
 };
 
 // inclusive block scan of one value per thread; returns the thread's inclusive
@@ -149,12 +161,16 @@ __global__ __launch_bounds__(kExpandBlock) void split_solve_expand(ExpandArgs a)
     u32* tasks = a.s.tasks + pos * a.npp;
     PosHdr* hdr = a.s.hdr + pos;
     const ulonglong2 b = reinterpret_cast<const ulonglong2*>(a.boards)[pos];
-    const u32 cls = oths::classify(b.x, b.y, 64 - __popcll(b.x | b.y), a.max_empties);
+    u32 cls = oths::classify(b.x, b.y, 64 - __popcll(b.x | b.y), a.max_empties);
+    const int ra = a.alpha ? (int)a.alpha[pos] : -othe::kInf;
+    const int rb = a.beta ? (int)a.beta[pos] : othe::kInf;
+    if (cls == oths::kSolved && !oths::window_ok(ra, rb)) cls = oths::kBadWindow;
     if (cls != oths::kSolved) {  // (uniform over the block)
         if (tid == 0) {
             emit(a.out, pos, 0, oths::kNoMove, cls, 0);
             hdr->nodes = 0;
             hdr->ntasks = 0;
+            hdr->window = othe::pack_window(-othe::kInf, othe::kInf);
         }
         return;
     }
@@ -228,10 +244,11 @@ __global__ __launch_bounds__(kExpandBlock) void split_solve_expand(ExpandArgs a)
         } else if (ntasks == 0) {  // the game ends inside the expanded plies everywhere
             int value;
             u32 mv, st;
-            othe::root_result<DeviceAtomics>(slab, value, mv, st);
+            othe::root_result_window<DeviceAtomics>(slab, value, mv, st, ra, rb);
             emit(a.out, pos, value, mv, st, end - 1);
         }
         hdr->ntasks = ntasks;
+        hdr->window = othe::pack_window(ra, rb);
     }
 }
 
@@ -550,21 +567,125 @@ __global__ __launch_bounds__(kTaskBlock) void split_solve_tasks_hashed(TaskArgs 
     }
 }
 
-// one cache for split_solve_tasks (order 0), one for the ordered kernel (1),
-// two for their hashed twins
-othd::ResidentBlocks g_resident[4];
-
-int resident_blocks(int order, bool hashed) {
-    const void* kernel =
-        hashed ? (order ? reinterpret_cast<const void*>(split_solve_tasks_hashed<true>)
-                        : reinterpret_cast<const void*>(split_solve_tasks_hashed<false>))
-               : (order ? reinterpret_cast<const void*>(split_solve_tasks_ordered)
-                        : reinterpret_cast<const void*>(split_solve_tasks));
-    return g_resident[order + (hashed ? 2 : 0)].get(kernel, kTaskBlock);
+// ------------------------------------------------------------------ tasks under a root window
+// othw_solve_split's task launch: the loop above once more, with every task's
+// window derived under its root's own (the position's header has it) and the
+// root's answer clamped into it (solve_tree_core.hpp's window_rooted and
+// root_result_window).  One body for the four kernels, plain or
+// hashed x either move order: they have no earlier code to keep, and the three
+// kernels above, which the calls without a window launch, stay what they were.
+template <bool kOrdered, bool kHashed>
+__global__ __launch_bounds__(kTaskBlock) void split_window_tasks(TaskArgs a, othh::Table tab) {
+    __shared__ u32 frames[oths::kFrames * oths::kFields * kTaskBlock];
+    const u32 lane = threadIdx.x;
+    const u64 ntasks = a.s.tbase[a.n];
+    const u64 total = ntasks + a.lanes;
+    LdsStack stk{frames + lane};
+    oths::Lane L;
+    L.depth = -1;
+    othm::Order Q;
+    othm::order_reset(Q);
+    u64 pos = 0;
+    u32 node = 0;
+    bool exhausted = false;  // the lane has made its failing request
+    for (;;) {
+        const bool idle = L.depth < 0;
+        const bool want = idle && !exhausted;
+        const u64 wantm = __ballot(want);
+        const u64 busym = __ballot(!idle);
+        if ((wantm | busym) == 0) break;
+        const u64 cnt = (u64)__popcll(wantm);
+        bool done = false;  // the lane's task ended in this turn of the loop
+        int v = 0;
+        u64 lim = 0;
+        u32 spent = 0;
+        if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
+            u64 base = 0;
+            if (lane == 0) {
+                base = atomicAdd(a.work, cnt);
+                if (base + cnt == total) atomicExch(a.work, 0ull);  // every request is made: reset
+            }
+            base = __shfl(base, 0);
+            if (want) {
+                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
+                if (g >= ntasks) {
+                    exhausted = true;
+                } else {
+                    u64 lo = 0, hi = a.n;  // the last position whose first task is <= g
+                    while (hi - lo > 1) {
+                        const u64 mid = (lo + hi) >> 1;
+                        if (a.s.tbase[mid] <= g) lo = mid; else hi = mid;
+                    }
+                    pos = lo;
+                    node = a.s.tasks[pos * a.npp + (g - a.s.tbase[pos])];
+                    Node* slab = a.s.nodes + pos * a.npp;
+                    int alpha, beta;
+                    const u32 rw = a.s.hdr[pos].window;
+                    othe::window_rooted<DeviceAtomics>(slab, node, kShareBounds, alpha, beta, othe::window_alpha(rw),
+                                                       othe::window_beta(rw));
+                    if (alpha >= beta) {  // cut off before it began: it reports its beta
+                        done = true;
+                        v = beta;
+                    } else {
+                        othe::start_task(L, slab[node], alpha, beta);
+                        othm::order_reset(Q);
+                    }
+                }
+            }
+        }
+        if (L.depth >= 0) {
+            if constexpr (kOrdered && kHashed)
+                othh::advance_ordered_hashed<DeviceRules, DeviceHashAtomics>(L, Q, stk, tab, a.limit);
+            else if constexpr (kHashed)
+                othh::advance_hashed<DeviceRules, DeviceHashAtomics>(L, stk, tab, a.limit);
+            else if constexpr (kOrdered)
+                oths::advance_ordered<DeviceRules>(L, Q, stk, a.limit);
+            else
+                oths::advance<DeviceRules>(L, stk, a.limit);
+            if (L.depth < 0) {
+                done = true;
+                v = L.value;
+                lim = L.status == oths::kLimit ? othe::kLimitBit : 0ull;
+                spent = L.nodes;
+            }
+        }
+        if (done) {
+            Node* slab = a.s.nodes + pos * a.npp;
+            PosHdr* hdr = a.s.hdr + pos;
+            const u64 before = __hip_atomic_fetch_add(&hdr->nodes, (unsigned long long)spent, __ATOMIC_RELAXED,
+                                                      __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("" ::"v"(before) : "memory");
+            if (othe::fold_up<DeviceAtomics>(slab, node, v, lim)) {
+                int value;
+                u32 mv, st;
+                othe::root_result_window<DeviceAtomics>(slab, value, mv, st, othe::window_alpha(hdr->window),
+                                                        othe::window_beta(hdr->window));
+                emit(a.out, pos, value, mv, st,
+                     __hip_atomic_load(&hdr->nodes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            }
+        }
+    }
 }
 
-int task_grid(int64_t tasks, int order, bool hashed = false) {
-    const int resident = resident_blocks(order, hashed);
+// one cache for split_solve_tasks (order 0), one for the ordered kernel (1),
+// two for their hashed twins, four for the kernels under a root window
+othd::ResidentBlocks g_resident[8];
+
+int resident_blocks(int order, bool hashed, bool windowed) {
+    const void* kernel =
+        windowed ? (hashed ? (order ? reinterpret_cast<const void*>(split_window_tasks<true, true>)
+                                    : reinterpret_cast<const void*>(split_window_tasks<false, true>))
+                           : (order ? reinterpret_cast<const void*>(split_window_tasks<true, false>)
+                                    : reinterpret_cast<const void*>(split_window_tasks<false, false>)))
+        : hashed ? (order ? reinterpret_cast<const void*>(split_solve_tasks_hashed<true>)
+                          : reinterpret_cast<const void*>(split_solve_tasks_hashed<false>))
+                 : (order ? reinterpret_cast<const void*>(split_solve_tasks_ordered)
+                          : reinterpret_cast<const void*>(split_solve_tasks));
+    return g_resident[order + (hashed ? 2 : 0) + (windowed ? 4 : 0)].get(kernel, kTaskBlock);
+}
+
+int task_grid(int64_t tasks, int order, bool hashed = false, bool windowed = false) {
+    const int resident = resident_blocks(order, hashed, windowed);
     if (resident <= 0) return -1;
     const int cap = std::min(std::max(env_int("OTH_SOLVE_BLOCKS", resident), 1), resident);
     return (int)std::min<int64_t>(std::max<int64_t>((tasks + kTaskBlock - 1) / kTaskBlock, 1), (int64_t)cap);
@@ -577,8 +698,11 @@ int64_t slab_nodes(int64_t n, int64_t npp) {
     return n * npp;
 }
 
-// othe_solve's launches; with a table the task launch is the hashed kernel's
-int launch_solve(const uint64_t* boards, const uint8_t* turn, int max_empties, int task_empties, int order,
+// othe_solve's launches; with a table the task launch is the hashed kernel's,
+// and `windowed` (othw_solve_split; alpha / beta NULL: the window's full end)
+// the kernels' under a root window
+int launch_solve(const uint64_t* boards, const uint8_t* turn, bool windowed, const int8_t* alpha, const int8_t* beta,
+                 int max_empties, int task_empties, int order,
                  uint32_t node_limit, int8_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes, void* scratch,
                  int64_t scratch_bytes, int32_t nodes_per_position, uint64_t* work, int64_t n, const othh::Table* tab,
                  void* stream) {
@@ -592,7 +716,7 @@ int launch_solve(const uint64_t* boards, const uint8_t* turn, int max_empties, i
     if (!scratch || ((uintptr_t)scratch & 7) || scratch_bytes < scratch_layout(n, nodes_per_position, nullptr, nullptr))
         return OTH_EINVAL;
     // a position has no more tasks than its slab holds
-    const int grid = task_grid(total_nodes, order, tab != nullptr);
+    const int grid = task_grid(total_nodes, order, tab != nullptr, windowed);
     if (grid <= 0) return status_of(hipErrorInvalidDevice);
     hipStream_t st = (hipStream_t)stream;
     Outputs out{value, best_move, status, nodes};
@@ -604,6 +728,8 @@ int launch_solve(const uint64_t* boards, const uint8_t* turn, int max_empties, i
     e.npp = (u32)nodes_per_position;
     e.max_empties = max_empties;
     e.task_empties = task_empties;
+    e.alpha = alpha;
+    e.beta = beta;
     split_solve_expand<<<(unsigned)n, kExpandBlock, 0, st>>>(e);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return status_of(err);
@@ -618,7 +744,16 @@ int launch_solve(const uint64_t* boards, const uint8_t* turn, int max_empties, i
     t.lanes = (u64)grid * kTaskBlock;
     t.npp = (u32)nodes_per_position;
     t.limit = node_limit ? node_limit : OTHS_DEFAULT_NODE_LIMIT;
-    if (tab && order)
+    const othh::Table none{nullptr, 0, 0};
+    if (windowed && tab && order)
+        split_window_tasks<true, true><<<(unsigned)grid, kTaskBlock, 0, st>>>(t, *tab);
+    else if (windowed && tab)
+        split_window_tasks<false, true><<<(unsigned)grid, kTaskBlock, 0, st>>>(t, *tab);
+    else if (windowed && order)
+        split_window_tasks<true, false><<<(unsigned)grid, kTaskBlock, 0, st>>>(t, none);
+    else if (windowed)
+        split_window_tasks<false, false><<<(unsigned)grid, kTaskBlock, 0, st>>>(t, none);
+    else if (tab && order)
         split_solve_tasks_hashed<true><<<(unsigned)grid, kTaskBlock, 0, st>>>(t, *tab);
     else if (tab)
         split_solve_tasks_hashed<false><<<(unsigned)grid, kTaskBlock, 0, st>>>(t, *tab);
@@ -627,6 +762,19 @@ int launch_solve(const uint64_t* boards, const uint8_t* turn, int max_empties, i
     else
         split_solve_tasks<<<(unsigned)grid, kTaskBlock, 0, st>>>(t);
     return status_of(hipGetLastError());
+}
+
+// othh_solve_hashed's checks of its table arguments; false: OTH_EINVAL
+bool make_table(int hash_bits, int hash_min_empties, void* table, int64_t table_bytes, othh::Table& tab) {
+    if (hash_bits < OTHH_MIN_BITS || hash_bits > OTHH_MAX_BITS || hash_min_empties < OTHH_MIN_EMPTIES_LO ||
+        hash_min_empties > OTHH_MIN_EMPTIES_HI)
+        return false;
+    if (!table || ((uintptr_t)table & (OTHH_ENTRY_BYTES - 1)) || table_bytes < ((int64_t)OTHH_ENTRY_BYTES << hash_bits))
+        return false;
+    tab.e = static_cast<othh::Entry*>(table);
+    tab.shift = 64 - hash_bits;
+    tab.min_empties = hash_min_empties;
+    return true;
 }
 
 }  // namespace
@@ -642,7 +790,7 @@ int othe_solve(const uint64_t* boards, const uint8_t* turn, int max_empties, int
                uint32_t node_limit, int8_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes,
                void* scratch, int64_t scratch_bytes, int32_t nodes_per_position, uint64_t* work, int64_t n,
                void* stream) {
-    return launch_solve(boards, turn, max_empties, task_empties, order, node_limit, value, best_move, status, nodes,
+    return launch_solve(boards, turn, false, nullptr, nullptr, max_empties, task_empties, order, node_limit, value, best_move, status, nodes,
                         scratch, scratch_bytes, nodes_per_position, work, n, nullptr, stream);
 }
 
@@ -655,17 +803,24 @@ int othh_solve_hashed(const uint64_t* boards, const uint8_t* turn, int max_empti
                       uint32_t node_limit, int8_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes,
                       void* scratch, int64_t scratch_bytes, int32_t nodes_per_position, uint64_t* work, int64_t n,
                       int hash_bits, int hash_min_empties, void* table, int64_t table_bytes, void* stream) {
-    if (hash_bits < OTHH_MIN_BITS || hash_bits > OTHH_MAX_BITS || hash_min_empties < OTHH_MIN_EMPTIES_LO ||
-        hash_min_empties > OTHH_MIN_EMPTIES_HI)
-        return OTH_EINVAL;
-    if (!table || ((uintptr_t)table & (OTHH_ENTRY_BYTES - 1)) || table_bytes < othh_hash_bytes(hash_bits))
-        return OTH_EINVAL;
     othh::Table tab;
-    tab.e = static_cast<othh::Entry*>(table);
-    tab.shift = 64 - hash_bits;
-    tab.min_empties = hash_min_empties;
-    return launch_solve(boards, turn, max_empties, task_empties, order, node_limit, value, best_move, status, nodes,
+    if (!make_table(hash_bits, hash_min_empties, table, table_bytes, tab)) return OTH_EINVAL;
+    return launch_solve(boards, turn, false, nullptr, nullptr, max_empties, task_empties, order, node_limit, value, best_move, status, nodes,
                         scratch, scratch_bytes, nodes_per_position, work, n, &tab, stream);
+}
+
+int othw_solve_split(const uint64_t* boards, const uint8_t* turn, int max_empties, int task_empties, int order,
+                     uint32_t node_limit, int8_t* value, uint8_t* best_move, uint8_t* status, uint32_t* nodes,
+                     void* scratch, int64_t scratch_bytes, int32_t nodes_per_position, uint64_t* work, int64_t n,
+                     const int8_t* alpha, const int8_t* beta, int hash_bits, int hash_min_empties, void* table,
+                     int64_t table_bytes, void* stream) {
+    if (!table && hash_bits == 0)
+        return launch_solve(boards, turn, true, alpha, beta, max_empties, task_empties, order, node_limit, value, best_move,
+                            status, nodes, scratch, scratch_bytes, nodes_per_position, work, n, nullptr, stream);
+    othh::Table tab;
+    if (!make_table(hash_bits, hash_min_empties, table, table_bytes, tab)) return OTH_EINVAL;
+    return launch_solve(boards, turn, true, alpha, beta, max_empties, task_empties, order, node_limit, value, best_move,
+                        status, nodes, scratch, scratch_bytes, nodes_per_position, work, n, &tab, stream);
 }
 
 int othe_solve_grid(int64_t tasks) {

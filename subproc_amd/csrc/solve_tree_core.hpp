@@ -108,6 +108,19 @@ OTHE_FN void window(Node* slab, u32 t, bool shared, int& alpha, int& beta) {
     othx::window<A, kInf>(slab, t, shared, alpha, beta);
 }
 
+// the same under the root's own window (ra, rb); with the full
+// one it computes what window() does
+template <class A>
+OTHE_FN void window_rooted(Node* slab, u32 t, bool shared, int& alpha, int& beta, int ra, int rb) {
+    othx::window<A, kInf, true>(slab, t, shared, alpha, beta, ra, rb);
+}
+
+// the root's window in one word (a position's header keeps it): the int8 halves
+// of a frame's packed window
+OTHE_FN u32 pack_window(int ra, int rb) { return (u32)(ra & 0xFF) | ((u32)(rb & 0xFF) << 8); }
+OTHE_FN int window_alpha(u32 w) { return (int)(int8_t)(w & 0xFF); }
+OTHE_FN int window_beta(u32 w) { return (int)(int8_t)((w >> 8) & 0xFF); }
+
 // a task enters the solver's state machine past its kRootNew step
 OTHE_FN void start_task(oths::Lane& L, const Node& x, int alpha, int beta) {
     L.P = x.P;
@@ -128,6 +141,28 @@ OTHE_FN void start_task(oths::Lane& L, const Node& x, int alpha, int beta) {
 template <class A>
 OTHE_FN void root_result(Node* slab, int& value, u32& move, u32& status) {
     othx::root_result<A>(slab, oths::kSolved, oths::kLimit, value, move, status);
+}
+
+// the completed root's answer under its window (ra, rb): the value clamped, and
+// for a root that has moves the lowest square whose child reaches the value
+// (the lowest maximiser inside the window, the lowest move that reaches rb on a
+// fail-high), none when no move beats ra.  With the full window it is
+// root_result()'s answer.
+template <class A>
+OTHE_FN void root_result_window(Node* slab, int& value, u32& move, u32& status, int ra, int rb) {
+    othx::root_result<A>(slab, oths::kSolved, oths::kLimit, value, move, status);
+    if (status != oths::kSolved) return;
+    const int best = value;
+    value = oths::clamp_to_window(best, ra, rb);
+    if ((slab[0].flags & kFinal) || slab[0].M == 0) return;
+    move = oths::kNoMove;
+    if (best <= ra) return;
+    const u32 f = slab[0].first_child, e = f + slab[0].nchild;
+    for (u32 c = f; c < e; c++)
+        if (-best_of(A::load(&slab[c].state)) >= value) {
+            move = slab[c].move;
+            break;
+        }
 }
 
 }  // namespace othe

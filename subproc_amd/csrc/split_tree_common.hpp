@@ -98,14 +98,36 @@ OTHX_FN bool fold_up(Node* slab, u32 i, int v, u64 lim) {
 // best, an odd one bounds beta by minus its best.  The ROOT hands down best - 1,
 // so that a root child that ties the maximum still comes back exact (the tie
 // rule).  With `shared` false the bests are the expansion's snapshot.
-template <class A, int kInf, class Node>
-OTHX_FN void window(Node* slab, u32 t, bool shared, int& alpha, int& beta) {
+//
+//
+// kRootWindow (the split solver's; the split search leaves it off and compiles
+// what it always did): (ra, rb) is the ROOT's own window, -kInf <= ra < rb <=
+// kInf, and with the full one every task's window is what it is without the
+// parameter.  The root is never cut off (all its children are resolved, so that
+// the lowest square that reaches rb can be read off them): it hands down rb as
+// one more bound, and max(ra, min(best, rb) - 1) for its best, so a root
+// child's window is never empty and is (rb - 1, rb) once the root has reached rb.
+template <class A, int kInf, bool kRootWindow = false, class Node>
+OTHX_FN void window(Node* slab, u32 t, bool shared, int& alpha, int& beta, int ra = -kInf, int rb = kInf) {
     alpha = -kInf;
     beta = kInf;
     bool odd = true;
     for (int i = slab[t].parent; i >= 0; i = slab[i].parent, odd = !odd) {
         int b = shared ? best_of(A::load(&slab[i].state)) : (int)slab[i].snap;
-        if (slab[i].parent < 0 && b > -kInf) b--;
+        if constexpr (kRootWindow) {
+            if (slab[i].parent < 0) {
+                if (b > rb) b = rb;
+                if (b > -kInf) b--;
+                if (b < ra) b = ra;
+                if (odd) {
+                    if (-rb > alpha) alpha = -rb;
+                } else if (rb < beta) {
+                    beta = rb;
+                }
+            }
+        } else {
+            if (slab[i].parent < 0 && b > -kInf) b--;
+        }
         if (odd) {
             if (-b < beta) beta = -b;
         } else if (b > alpha) {

@@ -39,6 +39,13 @@ orders the moves inside its tasks (default: ``--order``'s value);
 tasks a transposition table of 2**B entries (ops.SolveTable) that the engine
 keeps for its life, so successive ``go``s of one endgame reuse what the earlier
 ones solved: the same moves.
+``--solve-wld-empties W`` (W above ``--solve-empties``; at most 12, or 16 with
+``--solve-task-empties``) asks the solver who wins before the exact score is
+within reach: while more than K and at most W squares are empty, a ``go`` makes
+one win/draw/loss solve (ops.solve(wld=True)) with the exact solve's node
+limit, task settings and table.  On a proved win or draw the engine plays the
+solver's move (the lowest winning, resp. drawing, square); on a proved loss, a
+node limit or a tree that did not fit, the policy's move, as without the option.
 ``--policy search --depth D`` (D = 1..8) looks D plies ahead: the move is
 ops.search's, a fixed-depth alpha-beta with the eval table at the horizon (one
 launch per ``go``; depth 1 is the "eval" policy's move).  ``--solve-empties``
@@ -62,7 +69,7 @@ from .codec import handstr_from_coord
 
 class Engine:
     def __init__(self, name="GPU", policy="greedy", seed=0, weights=None, solve_empties=0, depth=1, split=0, order=0,
-                 solve_task_empties=None, solve_order=None, solve_hash_bits=None):
+                 solve_task_empties=None, solve_order=None, solve_hash_bits=None, solve_wld_empties=0):
         top = _lib.SOLVE_MAX_EMPTIES if solve_task_empties is None else _lib.SOLVE_TREE_MAX_EMPTIES
         if not 0 <= solve_empties <= top:
             raise ValueError(f"solve_empties must lie in 0..{top}" + (
@@ -77,6 +84,13 @@ class Engine:
                 raise ValueError("solve_hash_bits needs solve_task_empties: the table serves the split solver's tasks")
             if not _lib.SOLVE_HASH_MIN_BITS <= solve_hash_bits <= _lib.SOLVE_HASH_MAX_BITS:
                 raise ValueError(f"solve_hash_bits must lie in {_lib.SOLVE_HASH_MIN_BITS}..{_lib.SOLVE_HASH_MAX_BITS}")
+        if solve_wld_empties != 0:
+            if not 1 <= solve_wld_empties <= top:
+                raise ValueError(f"solve_wld_empties must lie in 1..{top}" + (
+                    "" if solve_task_empties is not None else
+                    f" (up to {_lib.SOLVE_TREE_MAX_EMPTIES} with solve_task_empties)"))
+            if solve_wld_empties <= solve_empties:
+                raise ValueError("solve_wld_empties must exceed solve_empties: below it the exact solve answers")
         if not 0 <= split <= _lib.TREE_MAX_SPLIT:
             raise ValueError(f"split must lie in 0..{_lib.TREE_MAX_SPLIT}")
         if not 1 <= depth <= _lib.SEARCH_MAX_DEPTH + split:
@@ -84,6 +98,7 @@ class Engine:
         if not 0 <= order <= _lib.ORDER_MAX:
             raise ValueError(f"order must lie in 0..{_lib.ORDER_MAX}")
         self.solve_empties = solve_empties
+        self.solve_wld_empties = solve_wld_empties
         self.solve_task_empties = solve_task_empties
         # (the solver's tasks take the search's --order unless --solve-order says otherwise)
         self.solve_order = (order if solve_order is None else solve_order) if solve_task_empties is not None else 0
@@ -130,10 +145,14 @@ class Engine:
     def _choose_solved(self):
         """The solver's move for the side to move (one oths_solve launch, or
         othe_solve's with solve_task_empties), or None when it gives none (more
-        than solve_empties empties; a node limit; a tree that did not fit)."""
+        than solve_empties empties; a node limit; a tree that did not fit).
+        With more than solve_empties and at most solve_wld_empties empties the
+        one solve is for win / draw / loss: its move, or None on a proved loss."""
         b = self.board
         bl, wh = b.bitboards()
-        if 64 - bin(bl | wh).count("1") > self.solve_empties:
+        empties = 64 - bin(bl | wh).count("1")
+        wld = empties > self.solve_empties
+        if empties > (self.solve_wld_empties if wld else self.solve_empties):
             return None
         dev = torch.device("cuda", torch.cuda.current_device())
         boards = ops.from_numpy_u64(np.array([[bl, wh]], np.uint64), dev)
@@ -142,8 +161,9 @@ class Engine:
         # empties in DESIGN.md §12's samples -- falls back to the policy)
         if self.solve_hash_bits is not None and self._solve_table is None:
             self._solve_table = ops.SolveTable(self.solve_hash_bits, dev)
-        r = ops.solve(boards, side, max_empties=self.solve_empties, node_limit=1 << 24,
-                      task_empties=self.solve_task_empties, order=self.solve_order, table=self._solve_table)
+        r = ops.solve(boards, side, max_empties=self.solve_wld_empties if wld else self.solve_empties,
+                      node_limit=1 << 24, task_empties=self.solve_task_empties, order=self.solve_order,
+                      table=self._solve_table, wld=wld)
         sq = int(r.best_move.cpu()[0])
         if int(r.status.cpu()[0]) != _lib.SOLVE_SOLVED or sq > 63:
             return None
@@ -170,7 +190,7 @@ class Engine:
         puts = b.puttables(b.turn)
         if not puts:
             return "PS"
-        if self.solve_empties > 0 and b.turn in (gboard.Black, gboard.White):
+        if (self.solve_empties > 0 or self.solve_wld_empties > 0) and b.turn in (gboard.Black, gboard.White):
             mv = self._choose_solved()
             if mv is not None:
                 return mv
@@ -202,8 +222,11 @@ class Engine:
             if self.policy == "search":
                 extra = " depth=%d" % self.depth + (" split=%d" % self.split if self.split > 0 else "") + (
                     " order=%d" % self.order if self.order > 0 else "") + extra
-            if self.solve_empties > 0:
-                extra += " solve_empties=%d" % self.solve_empties
+            if self.solve_empties > 0 or self.solve_wld_empties > 0:
+                if self.solve_empties > 0:
+                    extra += " solve_empties=%d" % self.solve_empties
+                if self.solve_wld_empties > 0:
+                    extra += " solve_wld_empties=%d" % self.solve_wld_empties
                 if self.solve_task_empties is not None:
                     extra += " solve_task_empties=%d" % self.solve_task_empties + (
                         " solve_order=%d" % self.solve_order if self.solve_order > 0 else "") + (
@@ -258,12 +281,15 @@ def main(argv=None):
     p.add_argument("--solve-hash-bits", type=int, default=None, metavar="B",
                    help="give the split solver's tasks a transposition table of 2**B entries, kept between moves "
                         "(4..26; needs --solve-task-empties)")
+    p.add_argument("--solve-wld-empties", type=int, default=0, metavar="W",
+                   help="with more than K and at most W empty squares, solve for win / draw / loss and play the proved "
+                        "winning or drawing move (0 = never; W > K, max 12, max 16 with --solve-task-empties)")
     a = p.parse_args(argv)
     if a.solve_hash_bits is not None and a.solve_task_empties is None:
         p.error("--solve-hash-bits needs --solve-task-empties")
     weights = params.read_paramgen(a.params)[1] if a.params else None
     eng = Engine(a.name, a.policy, a.seed, weights, a.solve_empties, a.depth, a.split, a.order,
-                 a.solve_task_empties, a.solve_order, a.solve_hash_bits)
+                 a.solve_task_empties, a.solve_order, a.solve_hash_bits, a.solve_wld_empties)
 
     def out(s):
         sys.stdout.write(s + "\n")

@@ -64,17 +64,20 @@ class VecEnv:
 
     def solve(self, max_empties=12, node_limit=0, task_empties=None, order=0,
               nodes_per_position=_lib.SOLVE_TREE_DEFAULT_NODES, table=None,
-              hash_min_empties=_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES):
+              hash_min_empties=_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES, window=None, wld=False):
         """Exact endgame solve of the current state (ops.solve): per game the
         disc difference under perfect play from the mover's side and the move
         that achieves it, for the games with at most `max_empties` empties.
         `task_empties` = T: the split solver, for a few games at a time and up
         to 16 empties; `order` = 1 orders the moves inside its tasks; `table`
         (an ops.SolveTable, kept by the caller) gives them a transposition
-        table, `hash_min_empties` its gate: the same answers."""
+        table, `hash_min_empties` its gate: the same answers.  `window` =
+        (alpha, beta), ints or int8 per-game tensors, asks for the value
+        clamped into the window only; `wld=True` is the window (-1, 1): who
+        wins, and a winning (or drawing) move."""
         return ops.solve(self.boards, self.turn, max_empties=max_empties, node_limit=node_limit,
                          task_empties=task_empties, order=order, nodes_per_position=nodes_per_position, table=table,
-                         hash_min_empties=hash_min_empties)
+                         hash_min_empties=hash_min_empties, window=window, wld=wld)
 
     def search(self, depth, weights=None, node_limit=0, split=0, order=0):
         """Depth-limited search of the current state (ops.search): per game the

@@ -19,6 +19,7 @@ Reference mapping (board.py line numbers):
   play    -> GameRunner matches between two such engines, whole games in one launch
 """
 import ctypes
+import numbers
 from collections import namedtuple
 
 import numpy as np
@@ -437,9 +438,41 @@ class SolveTable:
         self.data.zero_()
 
 
+def _solve_window(window, wld, n, d):
+    """:func:`solve`'s ``window`` / ``wld`` as (alpha, beta), each an int8 (n,)
+    device tensor or None (the full window's end); None: no window was given."""
+    if wld:
+        if window is not None:
+            raise ValueError("ops.solve: wld=True is window=(-1, 1); give one of the two")
+        window = (-1, 1)
+    if window is None:
+        return None
+    try:
+        lo, hi = window
+    except (TypeError, ValueError):
+        raise ValueError("window must be a pair (alpha, beta)") from None
+    ends = []
+    for name, x, full in (("alpha", lo, _lib.SOLVE_ALPHA_MIN), ("beta", hi, _lib.SOLVE_BETA_MAX)):
+        if isinstance(x, torch.Tensor):
+            _dev(x, "window " + name, torch.int8, (n,), d)
+            ends.append(x)
+        else:
+            if isinstance(x, bool) or not isinstance(x, numbers.Integral):
+                raise ValueError(f"window {name} must be an int or an int8 ({n},) device tensor")
+            if not _lib.SOLVE_ALPHA_MIN <= int(x) <= _lib.SOLVE_BETA_MAX:
+                raise ValueError(f"window {name} must lie in {_lib.SOLVE_ALPHA_MIN}..{_lib.SOLVE_BETA_MAX}")
+            ends.append(int(x))
+    if not isinstance(ends[0], torch.Tensor) and not isinstance(ends[1], torch.Tensor) and ends[0] >= ends[1]:
+        raise ValueError("window needs alpha < beta")
+    # an int at the full window's end is the C-ABI's NULL; any other is spread over the batch
+    return tuple(x if isinstance(x, torch.Tensor) else None if x == full
+                 else torch.full((n,), x, dtype=torch.int8, device=d)
+                 for x, full in zip(ends, (_lib.SOLVE_ALPHA_MIN, _lib.SOLVE_BETA_MAX)))
+
+
 def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=None, task_empties=None, order=0,
           nodes_per_position=_lib.SOLVE_TREE_DEFAULT_NODES, table=None,
-          hash_min_empties=_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES):
+          hash_min_empties=_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES, window=None, wld=False):
     """Exact endgame solve (oths_solve, include/othello_solve.h): for every
     position with at most ``max_empties`` (0..12) empty squares, the final disc
     difference under perfect play by both sides, from the mover's side (White
@@ -482,8 +515,25 @@ def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=Non
     same with any table, of any size and contents, and any ``hash_min_empties``
     (only a position within reach of ``node_limit`` may end differently): both
     are speed knobs.  Keep the table between calls to reuse what was solved.
+
+    ``window`` = (alpha, beta), -65 <= alpha < beta <= 65 from the mover's
+    side, asks a cheaper question (othw_solve / othw_solve_split,
+    include/othello_solve_window.h); each member is an int or an int8 (n,)
+    device tensor, one window per position.  With V the exact value: ``value``
+    is clamp(V, alpha, beta); ``best_move`` is the lowest maximiser when
+    alpha < V < beta, the lowest move whose own value reaches beta when
+    V >= beta, and 255 when V <= alpha (no move is proved); a forced pass is 64
+    and a finished game 255 whatever the window.  ``wld=True`` is
+    ``window=(-1, 1)``: the value is the sign of V, the move the lowest winning
+    move, the lowest drawing move, or 255 on a loss.  Ints out of range raise
+    ValueError; tensors are checked on the device, and a position whose window
+    is out of range or empty ends as _lib.SOLVE_BADWINDOW (value 0, move 255).
+    It works with and without ``task_empties``, ``order`` and ``table``; the
+    answers do not depend on them.  Without a window the calls are the ones
+    above, unchanged.
     """
     n = _n(boards)
+    win = _solve_window(window, bool(wld), n, boards.device)
     capturing = torch.cuda.is_current_stream_capturing()
     if work is None and capturing:
         raise RuntimeError("ops.solve under graph capture needs an explicit work word: an int64 (1,) device "
@@ -502,7 +552,7 @@ def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=Non
             raise ValueError(f"table is on {table.device}, boards on {boards.device}")
     if task_empties is not None:
         return _solve_split(boards, turn, n, int(max_empties), int(task_empties), int(order), int(node_limit),
-                            want_nodes, work, int(nodes_per_position), capturing, table, int(hash_min_empties))
+                            want_nodes, work, int(nodes_per_position), capturing, table, int(hash_min_empties), win)
     if int(order) != 0:
         raise ValueError("ops.solve orders moves only inside the split solver's tasks: order needs task_empties")
     d = boards.device
@@ -515,21 +565,27 @@ def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=Non
     w = work_word(d) if work is None else work
     pw = _dev(w, "work", torch.int64, (1,), d)
     with torch.cuda.device(d):
-        rc = _lib.load().oths_solve(pb, pt, int(max_empties), int(node_limit), val.data_ptr(), mv.data_ptr(),
-                                    st.data_ptr(), None if nd is None else nd.data_ptr(), pw, n, _stream())
+        out = (int(max_empties), int(node_limit), val.data_ptr(), mv.data_ptr(), st.data_ptr(),
+               None if nd is None else nd.data_ptr(), pw, n, _stream())
+        if win is None:
+            what = "oths_solve"
+            rc = _lib.load().oths_solve(pb, pt, *out)
+        else:
+            what = "othw_solve"
+            rc = _lib.load().othw_solve(pb, pt, *(None if x is None else x.data_ptr() for x in win), *out)
         if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
             if work is None:
                 _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
             elif not capturing:
                 w.zero_()
-        check(rc, "oths_solve")
+        check(rc, what)
     return SolveResult(val, mv, st, nd)
 
 
 def _solve_split(boards, turn, n, max_empties, task_empties, order, node_limit, want_nodes, work, nodes_per_position,
-                 capturing, table=None, hash_min_empties=_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES):
+                 capturing, table=None, hash_min_empties=_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES, win=None):
     """:func:`solve` with task_empties set: othe_solve on a scratch of its own
-    (othh_solve_hashed with a table)."""
+    (othh_solve_hashed with a table, othw_solve_split with a window)."""
     if capturing:
         raise RuntimeError("ops.solve(task_empties=...) allocates its scratch and does not run under graph capture")
     if not -2**31 <= nodes_per_position < 2**31:
@@ -552,7 +608,12 @@ def _solve_split(boards, turn, n, max_empties, task_empties, order, node_limit, 
         args = (pb, pt, max_empties, task_empties, order, node_limit, val.data_ptr(), mv.data_ptr(), st.data_ptr(),
                 None if nd is None else nd.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, nodes_per_position,
                 pw, n)
-        if table is None:
+        if win is not None:
+            what = "othw_solve_split"
+            tab = (0, 0, None, 0) if table is None else (table.bits, hash_min_empties, table.data.data_ptr(),
+                                                         table.nbytes)
+            rc = lib.othw_solve_split(*args, *(None if x is None else x.data_ptr() for x in win), *tab, _stream())
+        elif table is None:
             what = "othe_solve"
             rc = lib.othe_solve(*args, _stream())
         else:

@@ -17,6 +17,14 @@ position for "lane", per task otherwise); a method stops early once it has used
 --budget-s seconds and says how many launches it timed.  Nothing raises a
 limit silently: a position that ends as LIMIT or NOROOM is counted in
 status_counts and named in "unsolved".
+
+--window A,B / --wld / --around put every solve under a root window
+(ops.solve(window=...)): a fixed one, (-1, 1), or (V - 1, V + 1)
+per position with V from a full-window solve made before anything is timed.
+The line says which ("window"); the "search" method has no window and is left
+out.  --ladder K takes the first K ladder positions instead of 64 and --tile N
+repeats the set up to N positions (the one-lane solver's 32,768-position
+batches).
 """
 import argparse
 import json
@@ -38,9 +46,9 @@ def hashed_method(ops, a, e, te, o, bits, gate, kept):
     """ops.solve with a table of its own; the caller clears it between launches unless it is kept."""
     table = ops.SolveTable(bits, "cuda")
 
-    def fn(bb, tt):
+    def fn(bb, tt, **kw):
         return ops.solve(bb, tt, max_empties=e, node_limit=a.node_limit, want_nodes=True, task_empties=te, order=o,
-                         nodes_per_position=a.nodes_per_position, table=table, hash_min_empties=gate)
+                         nodes_per_position=a.nodes_per_position, table=table, hash_min_empties=gate, **kw)
 
     fn.table, fn.kept = table, kept
     return fn
@@ -61,38 +69,71 @@ def main():
     p.add_argument("--hash-bits", type=int, nargs="*", default=[], help="also time the split solver with a table of 2**B entries")
     p.add_argument("--hash-min-empties", type=int, nargs="+", default=[_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES])
     p.add_argument("--no-plain", action="store_true", help="skip the split lines without a table")
-    p.add_argument("--lib", default=None, help="another build of the library (the parent commit's: no table lines)")
+    p.add_argument("--lib", default=None, help="another build of the library (the parent commit's), for the methods it has")
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--window", default=None, metavar="A,B", help="solve under the root window (A, B)")
+    g.add_argument("--wld", action="store_true", help="solve for win / draw / loss: the window (-1, 1)")
+    g.add_argument("--around", action="store_true", help="solve under (V - 1, V + 1), V from a full-window solve")
+    p.add_argument("--ladder", type=int, default=64, help="ladder positions per empties to draw --positions from")
+    p.add_argument("--tile", type=int, default=0, help="repeat the position set up to this many positions")
     a = p.parse_args()
+    windowed = "wld" if a.wld else "around" if a.around else a.window
     if a.node_limit <= 0:
         p.error("every launch carries a node limit")
     if a.lib:
         _lib.LIB_PATH = os.path.abspath(a.lib)
-        _lib.SOLVE_HASH_SIGNATURES = {}  # (a build from before this set has nothing to bind it to)
-        if a.hash_bits:
-            p.error("--lib measures the methods the other build has: no --hash-bits")
+        import ctypes
+
+        other = ctypes.CDLL(_lib.LIB_PATH)
+        # (a build from before a set has nothing to bind it to)
+        if not hasattr(other, "othh_solve_hashed"):
+            _lib.SOLVE_HASH_SIGNATURES = {}
+        if not hasattr(other, "othw_solve"):
+            _lib.SOLVE_WINDOW_SIGNATURES = {}
+        if (a.hash_bits and not _lib.SOLVE_HASH_SIGNATURES) or (windowed and not _lib.SOLVE_WINDOW_SIGNATURES):
+            p.error("--lib measures the methods the other build has: it has no table / no window")
     import solve_cases
     from subproc_amd import ops
 
     sha = _lib.library_sha16(_lib.LIB_PATH)
     for e in sorted(a.empties):
-        b, t = solve_cases.ladder(e, 64)
+        b, t = solve_cases.ladder(e, a.ladder)
         k = min(a.positions, len(t))
-        boards = ops.from_numpy_u64(np.array(b[:k]), "cuda")
-        turn = torch.from_numpy(np.array(t[:k])).cuda()
+        b, t = np.array(b[:k]), np.array(t[:k])
+        if a.tile > k:
+            b, t = np.tile(b, (-(-a.tile // k), 1))[:a.tile], np.tile(t, -(-a.tile // k))[:a.tile]
+            k = a.tile
+        boards = ops.from_numpy_u64(b, "cuda")
+        turn = torch.from_numpy(t).cuda()
+        alpha = beta = None  # the windows, one per position
+        if windowed == "around":
+            exact = (ops.solve(boards, turn, max_empties=e, node_limit=a.node_limit) if e <= _lib.SOLVE_MAX_EMPTIES else
+                     ops.solve(boards, turn, max_empties=e, node_limit=a.node_limit, task_empties=8, order=1,
+                               table=ops.SolveTable(22, "cuda")))
+            assert bool((exact.status == 1).all()), "the full-window solve that --around centres on did not finish"
+            alpha, beta = (exact.value - 1).contiguous(), (exact.value + 1).contiguous()
+        elif windowed:
+            lo, hi = (-1, 1) if a.wld else (int(x) for x in a.window.split(","))
+            alpha = torch.full((k,), lo, dtype=torch.int8, device="cuda")
+            beta = torch.full((k,), hi, dtype=torch.int8, device="cuda")
+
+        def win(lo, hi):
+            return {} if alpha is None else {"window": (alpha[lo:hi], beta[lo:hi])}
+
         methods = []
         if "lane" in a.methods and e <= _lib.SOLVE_MAX_EMPTIES:
-            methods.append(("lane", lambda bb, tt: ops.solve(bb, tt, max_empties=e, node_limit=a.node_limit,
-                                                             want_nodes=True)))
-        if "search" in a.methods and 4 < e <= _lib.SEARCH_MAX_DEPTH + 4:
+            methods.append(("lane", lambda bb, tt, **kw: ops.solve(bb, tt, max_empties=e, node_limit=a.node_limit,
+                                                                   want_nodes=True, **kw)))
+        if "search" in a.methods and 4 < e <= _lib.SEARCH_MAX_DEPTH + 4 and not windowed:
             methods.append(("search", lambda bb, tt: ops.search(bb, tt, e, node_limit=a.node_limit, want_nodes=True,
                                                                 split=4, order=1)))
         if "split" in a.methods:
             for te in a.task_empties:
                 for o in a.order:
                     if not a.no_plain:
-                        methods.append(("T%do%d" % (te, o), lambda bb, tt, te=te, o=o: ops.solve(
+                        methods.append(("T%do%d" % (te, o), lambda bb, tt, te=te, o=o, **kw: ops.solve(
                             bb, tt, max_empties=e, node_limit=a.node_limit, want_nodes=True, task_empties=te, order=o,
-                            nodes_per_position=a.nodes_per_position)))
+                            nodes_per_position=a.nodes_per_position, **kw)))
                     for bits in a.hash_bits:
                         for gate in a.hash_min_empties:
                             for kept in (False, True):
@@ -100,7 +141,7 @@ def main():
                                                 hashed_method(ops, a, e, te, o, bits, gate, kept)))
         launches = [(i, i + a.batch) for i in range(0, k - a.batch + 1, a.batch)]
         for name, fn in methods:
-            fn(boards[:1], turn[:1])  # warm-up
+            fn(boards[:1], turn[:1], **win(0, 1))  # warm-up
             torch.cuda.synchronize()
             if hasattr(fn, "table"):
                 fn.table.clear()
@@ -111,7 +152,7 @@ def main():
                     fn.table.clear()
                     torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                r = fn(boards[lo:hi], turn[lo:hi])
+                r = fn(boards[lo:hi], turn[lo:hi], **win(lo, hi))
                 torch.cuda.synchronize()
                 ms.append((time.perf_counter() - t0) * 1e3)
                 nodes += int(r.nodes.cpu().numpy().view(np.uint32).astype(np.int64).sum())
@@ -121,7 +162,7 @@ def main():
                 unsolved += [lo + int(i) for i in np.nonzero(st != 1)[0]]
                 if time.perf_counter() - t_start > a.budget_s:
                     break
-            line = {"empties": e, "method": name, "batch": a.batch, "launches": len(ms), "of": len(launches),
+            line = {"empties": e, "method": name, "window": windowed, "batch": a.batch, "launches": len(ms), "of": len(launches),
                     "ms_median": statistics.median(ms), "ms_max": max(ms), "ms_sum": sum(ms), "nodes": nodes,
                     "status_counts": status, "unsolved": unsolved, "node_limit": a.node_limit,
                     "nodes_per_position": a.nodes_per_position if name.startswith("T") else None,
