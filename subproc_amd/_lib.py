@@ -17,6 +17,7 @@ ORDER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_order.h"
 SOLVE_TREE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve_tree.h")
 SOLVE_HASH_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve_hash.h")
 SOLVE_WINDOW_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve_window.h")
+MOVES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_moves.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -59,6 +60,9 @@ SOLVE_HASH_MIN_EMPTIES_LO, SOLVE_HASH_MIN_EMPTIES_HI = 1, 12
 SOLVE_HASH_DEFAULT_MIN_EMPTIES = 8
 SOLVE_BADWINDOW = 5          # include/othello_solve.h, set by the calls of include/othello_solve_window.h
 SOLVE_ALPHA_MIN, SOLVE_BETA_MAX = -65, 65
+MOVES_NOT_A_MOVE, MOVES_UNKNOWN = -128, -127  # include/othello_moves.h: the exact calls' int8 rows
+MOVES_NOT_A_MOVE32, MOVES_UNKNOWN32 = -2**31, -2**31 + 1  # the search's int32 rows
+MOVES_SEARCH_SLOTS = 64
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -165,6 +169,17 @@ SOLVE_WINDOW_SIGNATURES = {
                               _P, _P, _I, _I, _P, _I64, _P]),
 }
 
+# the value of every root move, include/othello_moves.h (its own prefix likewise)
+MOVES_SIGNATURES = {
+    "otha_solve_moves": (_I, [_P, _P, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P]),
+    "otha_solve_moves_scratch_bytes": (_I64, [_I64, _I]),
+    "otha_solve_moves_split": (_I, [_P, _P, _I, _I, _I, ctypes.c_uint32, ctypes.c_int32, _I, _I, _P, _I64, _P, _P, _P,
+                                    _P, _P, _P, _I64, _P, _I64, _P]),
+    "otha_solve_moves_split_scratch_bytes": (_I64, [_I64, _I, ctypes.c_int32]),
+    "otha_search_moves": (_I, [_P, _P, _I, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P]),
+    "otha_search_moves_scratch_bytes": (_I64, [_I64]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -197,7 +212,7 @@ def load():
         raise OthelloLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES, **PLAY_SIGNATURES,
                               **TREE_SIGNATURES, **ORDER_SIGNATURES, **SOLVE_TREE_SIGNATURES,
-                              **SOLVE_HASH_SIGNATURES, **SOLVE_WINDOW_SIGNATURES}.items():
+                              **SOLVE_HASH_SIGNATURES, **SOLVE_WINDOW_SIGNATURES, **MOVES_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import codec, ops
+from . import _lib
 from ._lib import BOOK_LINE, MOVES_STRIDE
 
 # Board() (board.py:22-27) as serialize_board writes it: Board.deserialize
@@ -101,6 +102,7 @@ class GameBooks:
 
     def __init__(self, moves, plies, start=None, start_turn=None):
         self.plies = plies
+        self.moves = moves
         self.n = moves.shape[0]
         self.pos = ops.replay_rows(moves, plies, start, start_turn)
         self._text = ops.book_text(self.pos.boards, self.pos.turn)  # one 67-byte line per recorded board
@@ -171,3 +173,34 @@ class GameBooks:
         """The slice of game g's rows in pos / features / the text lines."""
         r0, k = self._rows(g)
         return slice(r0, r0 + k)
+
+    def endgame_losses(self, max_empties=10, **solve_kw):
+        """The discs each endgame move gave away: an int8 tensor over the packed
+        rows.  A row is analysed when its game has a next row, the row has at
+        most ``max_empties`` empty squares and the move recorded from it is a
+        legal square for its mover; its entry is the position's exact value
+        minus the exact value of the move played (>= 0; 0: a best move; capped
+        at 127).  Every other row is -1: passes, ignored illegal codes, final
+        rows, rows with more empties, rows the solve did not finish (a node
+        limit, a tree that did not fit).  One ``ops.solve_moves`` call over the
+        selected rows; ``solve_kw`` are its keywords (``task_empties`` for more
+        than 12 empties, with a small ``nodes_per_position``; ``node_limit``,
+        ``order``, ``table`` ...)."""
+        boards, turn = self.pos.boards, self.pos.turn
+        dev = boards.device
+        rows = boards.shape[0]
+        plies = self.plies.long().clamp(max=MOVES_STRIDE)
+        game = torch.repeat_interleave(torch.arange(self.n, device=dev), plies + 1, output_size=rows)
+        ply = torch.arange(rows, device=dev) - self.pos.row_off[game]
+        code = self.moves[game, ply.clamp(max=MOVES_STRIDE - 1)].long()
+        counts = ops.result(boards)
+        empties = 64 - counts.n_black.long() - counts.n_white.long()
+        legal = (ops.legal(boards, turn) >> code.clamp(max=63)) & 1
+        idx = torch.nonzero((ply < plies[game]) & (empties <= int(max_empties)) & (code < 64) & (legal == 1)).reshape(-1)
+        out = torch.full((rows,), -1, dtype=torch.int8, device=dev)
+        r = ops.solve_moves(boards[idx].contiguous(), turn[idx].contiguous(), max_empties=max_empties, **solve_kw)
+        played = r.move_value[torch.arange(idx.numel(), device=dev), code[idx]].to(torch.int16)
+        loss = (r.value.to(torch.int16) - played).clamp(max=127)
+        known = (r.status == _lib.SOLVE_SOLVED) & (played > _lib.MOVES_UNKNOWN)
+        out[idx] = torch.where(known, loss, torch.full_like(loss, -1)).to(torch.int8)
+        return out

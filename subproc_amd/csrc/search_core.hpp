@@ -119,6 +119,18 @@ OTHM_FN void start(Lane& L, u64 P, u64 O, int plies) {
     L.status = kSearched;
 }
 
+// a root move's child (or the root after its forced pass) as a search of its
+// own, for the per-move values of include/othello_moves.h: P's owner is to
+// move and is NOT the root mover, so the root-side flag starts clear and every
+// leaf below is scored from O's owner's side.  M: P's moves, computed by the
+// caller (the kRootNew step would set the flag).  `plies` >= 1 are left below
+// this frame; the value comes out from P's owner's side.
+OTHM_FN void start_child(Lane& L, u64 P, u64 O, u64 M, int plies) {
+    start(L, P, O, plies);
+    L.M = M;
+    L.flags = M ? 0u : kFresh;
+}
+
 OTHM_FN void stop_at_limit(Lane& L) {
     L.depth = -1;
     L.value = 0;

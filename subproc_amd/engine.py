@@ -20,6 +20,11 @@ policy into GameRunner unchanged:
                    over (Player.show reads one line and looks for it, 92-95);
                    otherwise nothing (show_hamlet_param sends it unread, 70)
   quit          -> 1 line, exit                              (game_runner.py:56-64)
+  hint          -> Edax's name for it: one line "<move> <value>" per legal move of
+                   the side to move, best first (lowest square first among
+                   equals), or the one line "hint unavailable" (policies random
+                   and greedy outside --solve-empties); then an empty line.
+                   Nothing is played.  Player never sends it.
 
 Rules and move generation run on the GPU through the drop-in Board
 (subproc_amd.board); the move choice is the env's policy: "random" (uniform
@@ -185,6 +190,49 @@ class Engine:
             return None
         return handstr_from_coord(sq & 7, sq >> 3)
 
+    def _position(self):
+        """The board as a batch of one on the current device: (boards, side, empties)."""
+        bl, wh = self.board.bitboards()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        boards = ops.from_numpy_u64(np.array([[bl, wh]], np.uint64), dev)
+        side = torch.full((1,), self.board.turn, dtype=torch.uint8, device=dev)
+        return boards, side, 64 - bin(bl | wh).count("1")
+
+    def hint(self):
+        """The `hint` command's lines: "<move> <value>" for every legal move of
+        the side to move, best first and lowest square first among equals, or
+        ["hint unavailable"].  The values are ops.solve_moves' within
+        solve_empties (the engine's task, order and table settings; final disc
+        differences), else ops.search_moves' at the engine's depth (at most 8:
+        there is no split here) for policy search, else at depth 1 for policies
+        search and eval (the eval's units, 2**17 per disc where the game ends
+        inside the horizon); a row with an unknown move falls through to the
+        next source.  Policies random and greedy have no values of their own."""
+        b = self.board
+        if not b.puttables(b.turn) or b.turn not in (gboard.Black, gboard.White):
+            return []
+        boards, side, empties = self._position()
+        rows = []  # (row, the value that marks a square that is no move), lazily
+        if 0 < self.solve_empties and empties <= self.solve_empties:
+            if self.solve_hash_bits is not None and self._solve_table is None:
+                self._solve_table = ops.SolveTable(self.solve_hash_bits, boards.device)
+            rows.append(lambda: (ops.solve_moves(boards, side, max_empties=self.solve_empties, node_limit=1 << 24,
+                                                 task_empties=self.solve_task_empties, order=self.solve_order,
+                                                 table=self._solve_table), _lib.MOVES_NOT_A_MOVE, _lib.MOVES_UNKNOWN))
+        if self.policy in ("search", "eval"):
+            depths = [min(self.depth, _lib.SEARCH_MAX_DEPTH), 1] if self.policy == "search" else [1]
+            for d in dict.fromkeys(depths):
+                rows.append(lambda d=d: (ops.search_moves(boards, side, d, weights=self.weights, node_limit=1 << 24),
+                                         _lib.MOVES_NOT_A_MOVE32, _lib.MOVES_UNKNOWN32))
+        for source in rows:
+            r, no_move, unknown = source()
+            row = r.move_value[0].cpu().tolist()
+            if unknown in row:
+                continue
+            best = sorted((sq for sq in range(64) if row[sq] != no_move), key=lambda sq: (-row[sq], sq))
+            return ["%s %d" % (handstr_from_coord(sq & 7, sq >> 3).upper(), row[sq]) for sq in best]
+        return ["hint unavailable"]
+
     def choose(self):
         b = self.board
         puts = b.puttables(b.turn)
@@ -216,6 +264,10 @@ class Engine:
             self.board.put_s(mv.lower() if mv != "PS" else "PS")
             out("")
             out(">%s plays %s%s" % (self.name, color, mv.upper() if mv != "PS" else "PS"))
+            out("")
+        elif cmd == "hint":
+            for t in self.hint():
+                out(t)
             out("")
         elif cmd == "verbose p":
             extra = " weights=%s" % self.weights.reshape(-1).tolist() if self.policy in ("eval", "search") else ""

@@ -88,6 +88,26 @@ class VecEnv:
         return ops.search(self.boards, self.turn, depth, weights=weights, node_limit=node_limit, split=split,
                           order=order)
 
+    def solve_moves(self, max_empties=12, node_limit=0, want_nodes=False, task_empties=None, order=0,
+                    nodes_per_position=_lib.SOLVE_TREE_DEFAULT_NODES, table=None,
+                    hash_min_empties=_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES):
+        """The exact value of every legal move of the current state
+        (ops.solve_moves): per game a row of 64 values from the mover's side
+        (-128 where the square is no move) beside solve()'s value and move.
+        With `task_empties` every move slot costs a slab of
+        `nodes_per_position` nodes: pass a small one for many games."""
+        return ops.solve_moves(self.boards, self.turn, max_empties=max_empties, node_limit=node_limit,
+                               want_nodes=want_nodes, task_empties=task_empties, order=order,
+                               nodes_per_position=nodes_per_position, table=table, hash_min_empties=hash_min_empties)
+
+    def search_moves(self, depth, weights=None, node_limit=0, want_nodes=False):
+        """The `depth`-ply value of every legal move of the current state
+        (ops.search_moves), the leaves scored from the mover's side: per game a
+        row of 64 int32 values (-2**31 where the square is no move) beside
+        search()'s value and move."""
+        return ops.search_moves(self.boards, self.turn, depth, weights=weights, node_limit=node_limit,
+                                want_nodes=want_nodes)
+
     def books(self):
         """Book text (serialize_str, board.py:214-221) of every game: oth_book_text
         on the device, one 67-byte line per game, decoded on the host."""

@@ -744,6 +744,149 @@ def _search_split(boards, turn, n, depth, split, weights, node_limit, want_nodes
     return SearchResult(val, mv, st, nd)
 
 
+MovesResult = namedtuple("MovesResult", "move_value value best_move status nodes")
+
+
+def _moves_call(name, fn, size, head, boards, turn, n, dtype, want_nodes, work, capturing):
+    """The shared half of :func:`solve_moves` and :func:`search_moves`: the
+    outputs, a scratch of ``size`` bytes, the work word, and the call
+    ``fn(boards, turn, *head, move_value, value, best_move, status, nodes,
+    scratch, scratch_bytes, work, n, stream)``."""
+    d = boards.device
+    pb = _dev(boards, "boards", torch.int64)
+    pt = _dev(turn, "turn", torch.uint8, (n,), d)
+    if size < 0:
+        check(int(size), name + "_scratch_bytes")
+    rows = torch.empty((n, 64), dtype=dtype, device=d)
+    val = torch.empty(n, dtype=dtype, device=d)
+    mv = torch.empty(n, dtype=torch.uint8, device=d)
+    st = torch.empty(n, dtype=torch.uint8, device=d)
+    nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
+    scratch = torch.empty(max(int(size), 16) // 8, dtype=torch.int64, device=d)
+    w = work_word(d) if work is None else work
+    pw = _dev(w, "work", torch.int64, (1,), d)
+    with torch.cuda.device(d):
+        rc = fn(pb, pt, *head, rows.data_ptr(), val.data_ptr(), mv.data_ptr(), st.data_ptr(),
+                None if nd is None else nd.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, pw, n, _stream())
+        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
+            if work is None:
+                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
+            elif not capturing:
+                w.zero_()
+        check(rc, name)
+    # (the caching allocator hands the scratch to later work of THIS stream only)
+    return MovesResult(rows, val, mv, st, nd)
+
+
+def solve_moves(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=None, task_empties=None, order=0,
+                nodes_per_position=_lib.SOLVE_TREE_DEFAULT_NODES, table=None,
+                hash_min_empties=_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES):
+    """The exact value of EVERY root move (otha_solve_moves /
+    otha_solve_moves_split, include/othello_moves.h): :func:`solve`'s answer
+    for each position with at most ``max_empties`` empties, and beside it what
+    each legal move is worth.
+
+    Returns MovesResult(move_value int8 (n, 64), value int8, best_move uint8,
+    status uint8, nodes).  ``move_value[i, s]`` is the final disc difference
+    from the mover's side after playing square s, then perfect play by both
+    sides; _lib.MOVES_NOT_A_MOVE (-128) where s is not a legal move,
+    _lib.MOVES_UNKNOWN (-127) where the move's subtree hit ``node_limit`` (or,
+    split, did not fit its slab).  ``value``, ``best_move`` are :func:`solve`'s:
+    the row's maximum and its lowest maximising square; a forced pass has a row
+    of -128, move 64 and the passed position's value; a finished game its disc
+    difference and move 255; a row with an unknown move 0 and 255.  ``status``
+    is SOLVE_SKIPPED / SOLVE_INVALID as in :func:`solve` (rows all -128), else
+    the largest status among the position's moves (SOLVED < LIMIT < NOROOM).
+    ``node_limit`` bounds each root move's subtree, not the position;
+    ``nodes`` (with ``want_nodes``) counts the root moves and their subtrees.
+
+    ``task_empties``, ``order``, ``nodes_per_position``, ``table`` and
+    ``hash_min_empties`` are :func:`solve`'s: with ``task_empties`` every root
+    move is solved by the split solver (``max_empties`` up to 16).  Every move
+    slot, max(max_empties, 1) per position, then costs a slab of
+    ``nodes_per_position`` nodes (52 B each): a batch wants a smaller
+    ``nodes_per_position`` than the default, which suits single positions
+    (16 slots x 3.25 MiB).  There is no root window here.
+
+    Argument checks and ``work`` as in :func:`solve`.  Both forms allocate
+    their scratch here (the caching allocator's memory, no synchronisation);
+    the one-lane form may be captured in a graph with an explicit work word —
+    the scratch then belongs to the graph's pool — the split form may not.
+    """
+    n = _n(boards)
+    if not 0 <= int(node_limit) < 2**32:
+        raise ValueError("node_limit must fit 32 bits")
+    if task_empties is None and int(order) != 0:
+        raise ValueError("ops.solve_moves orders moves only inside the split solver's tasks: order needs task_empties")
+    if table is not None:
+        if task_empties is None:
+            raise ValueError("ops.solve_moves' table serves the split solver's tasks: table needs task_empties")
+        if not isinstance(table, SolveTable):
+            raise TypeError("table must be an ops.SolveTable")
+        if not _lib.SOLVE_HASH_MIN_EMPTIES_LO <= int(hash_min_empties) <= _lib.SOLVE_HASH_MIN_EMPTIES_HI:
+            raise ValueError(f"hash_min_empties must lie in {_lib.SOLVE_HASH_MIN_EMPTIES_LO}.."
+                             f"{_lib.SOLVE_HASH_MIN_EMPTIES_HI}")
+        if table.device != boards.device:
+            raise ValueError(f"table is on {table.device}, boards on {boards.device}")
+    _dev(boards, "boards", torch.int64)  # (a host tensor is refused before anything asks the device)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if work is None and capturing:
+        raise RuntimeError("ops.solve_moves under graph capture needs an explicit work word: an int64 (1,) device "
+                           "tensor zeroed before the capture, one per captured launch")
+    lib = _lib.load()
+    if task_empties is None:
+        return _moves_call("otha_solve_moves", lib.otha_solve_moves,
+                           lib.otha_solve_moves_scratch_bytes(n, int(max_empties)),
+                           (int(max_empties), int(node_limit)), boards, turn, n, torch.int8, want_nodes, work, capturing)
+    if capturing:
+        raise RuntimeError("ops.solve_moves(task_empties=...) does not run under graph capture")
+    npp = int(nodes_per_position)
+    if not -2**31 <= npp < 2**31:
+        raise ValueError("nodes_per_position must fit 32 bits")
+    tab = (0, 0, None, 0) if table is None else (table.bits, int(hash_min_empties), table.data.data_ptr(),
+                                                 table.nbytes)
+    return _moves_call("otha_solve_moves_split", lib.otha_solve_moves_split,
+                       lib.otha_solve_moves_split_scratch_bytes(n, int(max_empties), npp),
+                       (int(max_empties), int(task_empties), int(order), int(node_limit), npp, *tab), boards, turn, n,
+                       torch.int8, want_nodes, work, capturing)
+
+
+def search_moves(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, work=None):
+    """The depth-limited value of EVERY root move (otha_search_moves,
+    include/othello_moves.h): :func:`search`'s answer at ``depth`` (1..8), and
+    beside it what each legal move is worth to the root mover.
+
+    Returns MovesResult(move_value int32 (n, 64), value int32, best_move uint8,
+    status uint8, nodes).  ``move_value[i, s]`` is the depth - 1 search of the
+    position after square s WITH THE LEAVES SCORED FROM THE ROOT MOVER'S SIDE
+    (what a host loop of :func:`search` over the children cannot give: it
+    scores them from the child's mover's side, and the eval is not
+    antisymmetric); at depth 1 it is :func:`evaluate` of the child for the root
+    mover, or 2**17 times the disc difference where the game ends there.
+    _lib.MOVES_NOT_A_MOVE32 (-2**31) where s is not a legal move,
+    _lib.MOVES_UNKNOWN32 where the move's subtree hit ``node_limit``.
+    ``value``, ``best_move`` and ``status`` are :func:`search`'s (a row with an
+    unknown move: 0, 255, SEARCH_LIMIT); ``node_limit`` bounds each root
+    move's subtree.  No ``split`` and no ``order`` here.
+
+    ``work`` as in :func:`search`.  The scratch (1.7 KB per position) is
+    allocated here; the call may be captured in a graph with an explicit work
+    word.
+    """
+    n = _n(boards)
+    if not 0 <= int(node_limit) < 2**32:
+        raise ValueError("node_limit must fit 32 bits")
+    _dev(boards, "boards", torch.int64)  # (a host tensor is refused before anything asks the device)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if work is None and capturing:
+        raise RuntimeError("ops.search_moves under graph capture needs an explicit work word: an int64 (1,) device "
+                           "tensor zeroed before the capture, one per captured launch")
+    lib = _lib.load()
+    return _moves_call("otha_search_moves", lib.otha_search_moves, lib.otha_search_moves_scratch_bytes(n),
+                       (int(depth), _weights_ptr(weights), int(node_limit)), boards, turn, n, torch.int32, want_nodes,
+                       work, capturing)
+
+
 PlayResult = namedtuple("PlayResult", "final_boards diff plies moves hist a_black status nodes")
 
 
@@ -957,6 +1100,7 @@ def from_numpy_u64(a, device="cuda"):
 
 
 __all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", "solve", "SolveTable", "search", "play",
+           "solve_moves", "search_moves", "MovesResult",
            "sample_midgame",
            "replay",
            "book_text", "features", "evaluate", "to_numpy_u64", "from_numpy_u64",
