@@ -18,6 +18,7 @@ SOLVE_TREE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_sol
 SOLVE_HASH_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve_hash.h")
 SOLVE_WINDOW_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve_window.h")
 MOVES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_moves.h")
+BUDGET_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_budget.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -180,6 +181,17 @@ MOVES_SIGNATURES = {
     "otha_search_moves_scratch_bytes": (_I64, [_I64]),
 }
 
+# the searches by node budget, include/othello_budget.h (its own prefix likewise): othm_search's arguments with
+# budget, budgets, order in place of node_limit and depth in front of status; otho_play_ordered's with budget_a,
+# budget_b after the depths
+BUDGET_SIGNATURES = {
+    "othb_search": (_I, [_P, _P, _I, _P, ctypes.c_uint32, _P, _I, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "othb_play": (_I, [_P, _P, _U64, _U64, _P, _P, _I, _I, ctypes.c_uint32, ctypes.c_uint32, _I, _I, _I, _I, _I,
+                       ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "othb_search_grid": (_I, [_I64]),
+    "othb_play_grid": (_I, [_I64]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -212,7 +224,8 @@ def load():
         raise OthelloLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES, **PLAY_SIGNATURES,
                               **TREE_SIGNATURES, **ORDER_SIGNATURES, **SOLVE_TREE_SIGNATURES,
-                              **SOLVE_HASH_SIGNATURES, **SOLVE_WINDOW_SIGNATURES, **MOVES_SIGNATURES}.items():
+                              **SOLVE_HASH_SIGNATURES, **SOLVE_WINDOW_SIGNATURES, **MOVES_SIGNATURES,
+                              **BUDGET_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -58,7 +58,11 @@ still takes precedence where it applies.  ``--split S`` (S = 1..4) makes that
 search the split search (ops.search(split=S)): the position's tree is spread
 over the whole device, and D may go to 8 + S.  ``--order 1`` searches with move
 ordering (ops.search(order=1), include/othello_order.h): the same moves from a
-smaller tree.
+smaller tree.  ``--nodes B`` (with ``--policy search``, without ``--split``)
+gives every ``go`` a budget of B nodes instead of a fixed depth: the move is
+ops.search_budget's, an iterative deepening whose deepest completed iteration
+answers, ``--depth`` (at most 8) being its cap; "verbose 1" then shows the depth
+the last search reached at the end of the board display's last line.
 """
 import argparse
 import random
@@ -74,7 +78,7 @@ from .codec import handstr_from_coord
 
 class Engine:
     def __init__(self, name="GPU", policy="greedy", seed=0, weights=None, solve_empties=0, depth=1, split=0, order=0,
-                 solve_task_empties=None, solve_order=None, solve_hash_bits=None, solve_wld_empties=0):
+                 solve_task_empties=None, solve_order=None, solve_hash_bits=None, solve_wld_empties=0, nodes=None):
         top = _lib.SOLVE_MAX_EMPTIES if solve_task_empties is None else _lib.SOLVE_TREE_MAX_EMPTIES
         if not 0 <= solve_empties <= top:
             raise ValueError(f"solve_empties must lie in 0..{top}" + (
@@ -102,6 +106,15 @@ class Engine:
             raise ValueError(f"depth must lie in 1..{_lib.SEARCH_MAX_DEPTH + split}")
         if not 0 <= order <= _lib.ORDER_MAX:
             raise ValueError(f"order must lie in 0..{_lib.ORDER_MAX}")
+        if nodes is not None:
+            if policy != "search" or split != 0:
+                raise ValueError("nodes applies to policy search without a split")
+            if not 1 <= nodes < 2**32:
+                raise ValueError("nodes must lie in 1..2**32 - 1")
+            if depth > _lib.SEARCH_MAX_DEPTH:
+                raise ValueError(f"with nodes, depth is the cap and must lie in 1..{_lib.SEARCH_MAX_DEPTH}")
+        self.nodes = nodes
+        self.reached = None  # the depth the last budget search reached
         self.solve_empties = solve_empties
         self.solve_wld_empties = solve_wld_empties
         self.solve_task_empties = solve_task_empties
@@ -183,8 +196,13 @@ class Engine:
         dev = torch.device("cuda", torch.cuda.current_device())
         boards = ops.from_numpy_u64(np.array([[bl, wh]], np.uint64), dev)
         side = torch.full((1,), b.turn, dtype=torch.uint8, device=dev)
-        r = ops.search(boards, side, self.depth, weights=self.weights, node_limit=1 << 24, split=self.split,
-                       order=self.order)
+        if self.nodes is not None:  # by budget: the deepest completed iteration's move
+            r = ops.search_budget(boards, side, self.nodes, max_depth=self.depth, weights=self.weights,
+                                  order=self.order)
+            self.reached = int(r.depth.cpu()[0])
+        else:
+            r = ops.search(boards, side, self.depth, weights=self.weights, node_limit=1 << 24, split=self.split,
+                           order=self.order)
         sq = int(r.best_move.cpu()[0])
         if int(r.status.cpu()[0]) != _lib.SEARCH_SEARCHED or sq > 63:
             return None
@@ -272,7 +290,8 @@ class Engine:
         elif cmd == "verbose p":
             extra = " weights=%s" % self.weights.reshape(-1).tolist() if self.policy in ("eval", "search") else ""
             if self.policy == "search":
-                extra = " depth=%d" % self.depth + (" split=%d" % self.split if self.split > 0 else "") + (
+                extra = " depth=%d" % self.depth + (" nodes=%d" % self.nodes if self.nodes is not None else "") + (
+                    " split=%d" % self.split if self.split > 0 else "") + (
                     " order=%d" % self.order if self.order > 0 else "") + extra
             if self.solve_empties > 0 or self.solve_wld_empties > 0:
                 if self.solve_empties > 0:
@@ -288,6 +307,8 @@ class Engine:
             b = self.board
             text = str(b).rstrip("\n").split("\n")[:12]
             text += [""] * (12 - len(text))
+            if self.nodes is not None and self.reached is not None:
+                text[11] = (text[11] + " " if text[11] else "") + "depth=%d" % self.reached
             won = ""
             if b.is_game_over() and b.n_black() != b.n_white():
                 won = "Black won" if b.n_black() > b.n_white() else "White won"
@@ -319,6 +340,8 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--params", default=None, help="eval table in the paramgen.py file format (policies eval and search)")
     p.add_argument("--depth", type=int, default=1, metavar="D", help="plies policy search looks ahead (1..8, with --split S 1..8+S)")
+    p.add_argument("--nodes", type=int, default=None, metavar="B",
+                   help="policy search by node budget: every go deepens until B nodes are spent, --depth is the cap")
     p.add_argument("--split", type=int, default=0, metavar="S",
                    help="spread policy search's tree over the device: its top S plies become tasks (0 = off, max 4)")
     p.add_argument("--order", type=int, choices=[0, 1], default=0,
@@ -341,7 +364,7 @@ def main(argv=None):
         p.error("--solve-hash-bits needs --solve-task-empties")
     weights = params.read_paramgen(a.params)[1] if a.params else None
     eng = Engine(a.name, a.policy, a.seed, weights, a.solve_empties, a.depth, a.split, a.order,
-                 a.solve_task_empties, a.solve_order, a.solve_hash_bits, a.solve_wld_empties)
+                 a.solve_task_empties, a.solve_order, a.solve_hash_bits, a.solve_wld_empties, a.nodes)
 
     def out(s):
         sys.stdout.write(s + "\n")

@@ -88,6 +88,14 @@ class VecEnv:
         return ops.search(self.boards, self.turn, depth, weights=weights, node_limit=node_limit, split=split,
                           order=order)
 
+    def search_budget(self, budget, max_depth=8, weights=None, order=0, want_nodes=False):
+        """Search of the current state by node budget (ops.search_budget): per
+        game the value and move of the deepest iteration of an iterative
+        deepening that fitted `budget` nodes (an int, or one per game), with the
+        depth it reached; `max_depth` caps the depth."""
+        return ops.search_budget(self.boards, self.turn, budget, max_depth=max_depth, weights=weights, order=order,
+                                 want_nodes=want_nodes)
+
     def solve_moves(self, max_empties=12, node_limit=0, want_nodes=False, task_empties=None, order=0,
                     nodes_per_position=_lib.SOLVE_TREE_DEFAULT_NODES, table=None,
                     hash_min_empties=_lib.SOLVE_HASH_DEFAULT_MIN_EMPTIES):

@@ -744,6 +744,74 @@ def _search_split(boards, turn, n, depth, split, weights, node_limit, want_nodes
     return SearchResult(val, mv, st, nd)
 
 
+BudgetResult = namedtuple("BudgetResult", "value best_move status depth nodes")
+
+
+def search_budget(boards, turn, budget, max_depth=8, weights=None, order=0, want_nodes=False, work=None):
+    """Search by node budget (othb_search, include/othello_budget.h): every
+    position is searched by iterative deepening -- :func:`search` at depth 1,
+    2, ... up to ``max_depth`` (1..8) or the number of empty squares -- until the
+    next iteration would take the position past its ``budget`` of nodes (an int
+    >= 1 for all, or a uint32 / int64 tensor of n; a position with budget 0 is
+    not searched).  The answer is that of the deepest iteration that completed;
+    iteration d is exactly ``search(depth=d)``, so every field can be checked
+    against it.  A lane's work is bounded by its budget, whatever the position.
+
+    Returns BudgetResult(value int32, best_move uint8, status uint8, depth
+    uint8, nodes): ``depth`` is the deepest completed iteration; status is
+    _lib.SEARCH_SEARCHED, SEARCH_INVALID (black & white overlap) or SEARCH_LIMIT
+    (not even depth 1 fitted the budget: value 0, move 255, depth 0).  ``nodes``
+    (uint32 as int32 bits, with ``want_nodes``) sums the completed iterations,
+    so it never exceeds the budget.  ``order`` = 1 deepens with the ordered
+    search: the same value and move per depth, other node counts, so the depth
+    reached may differ.  ``work`` as in :func:`search`."""
+    n = _n(boards)
+    d = boards.device
+    pb = _dev(boards, "boards", torch.int64)
+    pt = _dev(turn, "turn", torch.uint8, (n,), d)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if work is None and capturing:
+        raise RuntimeError("ops.search_budget under graph capture needs an explicit work word: an int64 (1,) device "
+                           "tensor zeroed before the capture, one per captured launch")
+    per_position = None
+    if isinstance(budget, torch.Tensor):
+        if budget.dtype == torch.int64:
+            if capturing:
+                raise RuntimeError("ops.search_budget under graph capture takes a uint32 budget tensor")
+            if n and not bool(((budget >= 0) & (budget < 2**32)).all()):
+                raise ValueError("budget must fit 32 bits")
+            per_position = budget.to(torch.int32).view(torch.uint32)  # (the low 32 bits)
+        elif budget.dtype == torch.uint32:
+            per_position = budget
+        else:
+            raise TypeError(f"budget: expected an int or a uint32 / int64 tensor, got {budget.dtype}")
+        pbud = _dev(per_position, "budget", per_position.dtype, (n,), d)
+        scalar = 0
+    else:
+        scalar, pbud = int(budget), None
+        if not 1 <= scalar < 2**32:
+            raise ValueError("budget must lie in 1..2**32 - 1")
+    val = torch.empty(n, dtype=torch.int32, device=d)
+    mv = torch.empty(n, dtype=torch.uint8, device=d)
+    st = torch.empty(n, dtype=torch.uint8, device=d)
+    dp = torch.empty(n, dtype=torch.uint8, device=d)
+    nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
+    w = work_word(d) if work is None else work
+    pw = _dev(w, "work", torch.int64, (1,), d)
+    lib = _lib.load()
+    with torch.cuda.device(d):
+        rc = lib.othb_search(pb, pt, int(max_depth), _weights_ptr(weights), scalar, pbud, int(order), val.data_ptr(),
+                             mv.data_ptr(), dp.data_ptr(), st.data_ptr(), None if nd is None else nd.data_ptr(), pw, n,
+                             _stream())
+        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
+            if work is None:
+                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
+            elif not capturing:
+                w.zero_()
+        check(rc, "othb_search")
+    return BudgetResult(val, mv, st, dp, nd)
+
+
 MovesResult = namedtuple("MovesResult", "move_value value best_move status nodes")
 
 
@@ -892,7 +960,7 @@ PlayResult = namedtuple("PlayResult", "final_boards diff plies moves hist a_blac
 
 def play(n, seed, game_id0=0, weights_a=None, weights_b=None, depth_a=1, depth_b=None, exact_empties=0, n_rand_a=0,
          n_rand_b=0, swap_colours=False, start=None, start_turn=None, record_moves=False, node_limit=0,
-         want_nodes=False, hist=None, device="cuda", work=None, order=0):
+         want_nodes=False, hist=None, device="cuda", work=None, order=0, budget=None):
     """n whole games between two searching players in one launch (othp_play,
     include/othello_play.h): :func:`rollout_runner`'s match schedule -- player
     A against player B, the colour draw, the random-move budgets -- with every
@@ -915,7 +983,19 @@ def play(n, seed, game_id0=0, weights_a=None, weights_b=None, depth_a=1, depth_b
     One lane plays one game: a launch lasts as long as its longest game.
     ``work`` as in :func:`rollout`.  ``order`` = 1: both players search with
     move ordering (otho_play_ordered, include/othello_order.h); the games are
-    the same move for move, ``nodes`` is smaller."""
+    the same move for move, ``nodes`` is smaller.
+
+    ``budget`` = B or (Ba, Bb), nodes per move (>= 1): every policy move is
+    :func:`search_budget`'s with the mover's budget, ``depth_a`` / ``depth_b``
+    being the depth caps (othb_play, include/othello_budget.h); the searches
+    from ``exact_empties`` on keep ``node_limit`` and take no budget; ``nodes``
+    sums the completed iterations.  A game then costs at most its plies times
+    the budget, whatever its positions.  None: today's fixed-depth games."""
+    budgets = ()
+    if budget is not None:
+        budgets = (int(budget),) * 2 if isinstance(budget, numbers.Integral) else tuple(int(b) for b in budget)
+        if len(budgets) != 2 or not all(1 <= b < 2**32 for b in budgets):
+            raise ValueError("budget must be an int or a pair (Ba, Bb) of ints in 1..2**32 - 1")
     capturing = torch.cuda.is_current_stream_capturing()
     if work is None and capturing:
         raise RuntimeError("ops.play under graph capture needs an explicit work word: an int64 (1,) device "
@@ -944,9 +1024,11 @@ def play(n, seed, game_id0=0, weights_a=None, weights_b=None, depth_a=1, depth_b
     lib = _lib.load()
     fn, name, ordered = (lib.otho_play_ordered, "otho_play_ordered", (int(order),)) if int(order) != 0 else (
         lib.othp_play, "othp_play", ())
+    if budgets:
+        fn, name, ordered = lib.othb_play, "othb_play", (int(order),)
     with torch.cuda.device(d):
         rc = fn(ps, pst, seed & (2**64 - 1), game_id0, _weights_ptr(weights_a), _weights_ptr(weights_b), int(depth_a),
-                int(depth_a if depth_b is None else depth_b), int(exact_empties), *ordered, int(n_rand_a),
+                int(depth_a if depth_b is None else depth_b), *budgets, int(exact_empties), *ordered, int(n_rand_a),
                 int(n_rand_b), int(bool(swap_colours)), int(node_limit), ab.data_ptr(), fb.data_ptr(), df.data_ptr(),
                 pl.data_ptr(), None if mv is None else mv.data_ptr(), st.data_ptr(),
                 None if nd is None else nd.data_ptr(), ph, pw, n, _stream())
@@ -1100,6 +1182,7 @@ def from_numpy_u64(a, device="cuda"):
 
 
 __all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", "solve", "SolveTable", "search", "play",
+           "search_budget", "BudgetResult",
            "solve_moves", "search_moves", "MovesResult",
            "sample_midgame",
            "replay",

@@ -36,14 +36,15 @@ MatchBatch = namedtuple("MatchBatch", "games books meta won stats a_black")
 N_RAND_HAND_UNTIL = 10  # game_runner.py:6
 
 
-def hamlet_param_line(name, policy, weights, depth=None, solve_empties=0):
+def hamlet_param_line(name, policy, weights, depth=None, solve_empties=0, nodes=None):
     """The 'verbose p' line of the GPU engine (subproc_amd.engine): what
     GameRunner.extract_hamlet_param stores as 'hamletparam' (game_runner.py:124-130).
     For policy "search": the engine's depth before the weights and, if set,
-    its solve_empties after them."""
+    its solve_empties after them; ``nodes``, the engine's --nodes budget, after
+    the depth (None: no budget, the text as it always was)."""
     extra = " weights=%s" % params.as_weights(weights).reshape(-1).tolist() if policy in ("eval", "search") else ""
     if policy == "search":
-        extra = " depth=%d" % depth + extra
+        extra = " depth=%d" % depth + (" nodes=%d" % nodes if nodes is not None else "") + extra
         if solve_empties > 0:
             extra += " solve_empties=%d" % solve_empties
     return "%s policy=%s%s" % (name, policy, extra)
@@ -51,7 +52,7 @@ def hamlet_param_line(name, policy, weights, depth=None, solve_empties=0):
 
 def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, policy="eval", name_a="Hamlet",
                name_b="GPU", device="cuda", record=True, win_rule="reference", store=None, depth=None,
-               exact_empties=0, order=0):
+               exact_empties=0, order=0, budget=None):
     """n GameRunner games between A (``weights_a``) and B (``weights_b``,
     default params.DEFAULT_WEIGHTS), both playing ``policy``: "greedy", "eval",
     or "search" -- every policy move searched ``depth`` plies deep (an int, or
@@ -59,6 +60,8 @@ def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, po
     empty squares on (ops.play: the whole games in one launch; ``order`` = 1: with
     move ordering, the same games from smaller trees).  A "search"
     game that a search's node limit stopped (ops.play's status) raises.
+    ``budget`` = B or (A's, B's): the moves are searched by node budget, ``depth``
+    being the cap (ops.play(budget=...)); None: fixed depth.
 
     Game i is global id ``game_id0 + i`` (its book id).  ``record=True``
     replays every game into books (the recorder's view); the batch stats are
@@ -75,15 +78,17 @@ def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, po
         if depth is None:
             raise ValueError("policy 'search' needs depth=D or depth=(Da, Db)")
         depth_a, depth_b = (depth, depth) if isinstance(depth, int) else depth
+        budget_a, budget_b = (budget, budget) if budget is None or isinstance(budget, int) else budget
         r = ops.play(n, seed, game_id0, wa, wb, depth_a, depth_b, exact_empties, n_rand_a, n_rand_b, swap,
-                     record_moves=record, device=device, order=order)
+                     record_moves=record, device=device, order=order,
+                     budget=None if budget is None else (budget_a, budget_b))
         if not bool((r.status == ops._lib.SEARCH_SEARCHED).all()):
             raise RuntimeError("do_matches: a game's search reached the node limit")
-        line = {"a": hamlet_param_line(name_a, policy, wa, depth_a, exact_empties),
-                "b": hamlet_param_line(name_b, policy, wb, depth_b, exact_empties)}
+        line = {"a": hamlet_param_line(name_a, policy, wa, depth_a, exact_empties, budget_a),
+                "b": hamlet_param_line(name_b, policy, wb, depth_b, exact_empties, budget_b)}
     else:
-        if depth is not None or exact_empties:
-            raise ValueError("depth and exact_empties apply to policy 'search' only")
+        if depth is not None or exact_empties or budget is not None:
+            raise ValueError("depth, exact_empties and budget apply to policy 'search' only")
         if order:
             raise ValueError("order applies to policy 'search' only")
         r = ops.rollout_runner(n, seed, game_id0, policy, wa, wb, n_rand_a, n_rand_b, swap, record_moves=record,
