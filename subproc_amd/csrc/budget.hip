@@ -33,6 +33,7 @@
 #include "../../include/othello_search.h"
 #include "device_common.hpp"
 #include "budget_core.hpp"
+#include "game_out.hpp"
 
 static_assert(OTHM_MAX_DEPTH == othm::kMaxDepth && OTHM_SEARCHED == othm::kSearched &&
                   OTHM_INVALID == othm::kInvalid && OTHM_LIMIT == othm::kLimit && OTHM_NO_MOVE == othm::kNoMove &&
@@ -49,7 +50,6 @@ using othm::u64;
 
 constexpr int kBudgetBlock = 64;  // one wave
 using othd::DeviceRules;
-using othd::env_int;
 using othd::kRefillMin;
 using othd::status_of;
 using LdsStack = othd::LdsStack9<kBudgetBlock>;
@@ -165,35 +165,9 @@ struct BudgetPlayArgs {
     int8_t w[2][OTH_EVAL_WEIGHTS];  // A's table, B's table
 };
 
-// a game's move record, as play.hip's: the row starts 255-padded, a move is one byte store
-struct MoveRecord {
-    uint8_t* row;  // NULL: no record
-    __device__ __forceinline__ void pad() const {
-        if (!row) return;
-#pragma unroll
-        for (int q = 0; q < OTH_MOVES_STRIDE / 16; q++) reinterpret_cast<uint4*>(row)[q] = make_uint4(~0u, ~0u, ~0u, ~0u);
-    }
-    __device__ __forceinline__ void move(u32 ply, u32 code) const {
-        if (row && ply < (u32)OTH_MOVES_STRIDE) row[ply] = (uint8_t)code;
-    }
-};
-
-// game g has ended (G.status says how): othp_play's outputs
-__device__ __forceinline__ void emit(const BudgetPlayArgs& a, u64 g, const othp::Game& G) {
-    const u64 bl = othp::black_of(G), wh = othp::white_of(G);
-    const int d = G.status == othm::kInvalid ? 0 : __popcll(bl) - __popcll(wh);
-    if (a.a_black) a.a_black[g] = (uint8_t)G.a_black;
-    if (a.final_boards) reinterpret_cast<ulonglong2*>(a.final_boards)[g] = make_ulonglong2(bl, wh);
-    if (a.diff) a.diff[g] = (int8_t)d;
-    if (a.plies) a.plies[g] = (uint8_t)G.ply;
-    if (a.status) a.status[g] = (uint8_t)G.status;
-    if (a.nodes) a.nodes[g] = G.nodes;
-    if (a.hist && G.status == othm::kSearched) {
-        atomicAdd(&a.hist[d + 64], 1ull);
-        atomicAdd(&a.hist[d > 0 ? 129 : (d < 0 ? 130 : 131)], 1ull);
-        atomicAdd(&a.hist[132], (unsigned long long)G.ply);
-    }
-}
+// the game's move record and othp_play's outputs: game_out.hpp
+using othp::emit;
+using othp::MoveRecord;
 
 // the persistent loop of both game kernels; kOrdered: order_core.hpp's machine
 template <bool kOrdered>
@@ -276,10 +250,7 @@ int grid_of(int64_t n, int play, int order) {
                       : reinterpret_cast<const void*>(budget_play_kernel))
              : (order ? reinterpret_cast<const void*>(budget_deepen_ordered_kernel)
                       : reinterpret_cast<const void*>(budget_deepen_kernel));
-    const int resident = g_resident[play][order].get(kernel, kBudgetBlock);
-    if (resident <= 0) return -1;
-    const int cap = std::min(std::max(env_int("OTH_BUDGET_BLOCKS", resident), 1), resident);
-    return (int)std::min<int64_t>((n + kBudgetBlock - 1) / kBudgetBlock, (int64_t)cap);
+    return othd::launch_grid(g_resident[play][order], kernel, kBudgetBlock, n, "OTH_BUDGET_BLOCKS");
 }
 
 }  // namespace
@@ -369,17 +340,11 @@ int othb_play(const uint64_t* start, const uint8_t* start_turn, uint64_t seed, u
 }
 
 int othb_search_grid(int64_t n) {
-    if (n < 0) return OTH_EINVAL;
-    if (n == 0) return 0;
-    const int grid = grid_of(n, 0, 0);
-    return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
+    return othd::grid_answer(n, [&] { return grid_of(n, 0, 0); });
 }
 
 int othb_play_grid(int64_t n) {
-    if (n < 0) return OTH_EINVAL;
-    if (n == 0) return 0;
-    const int grid = grid_of(n, 1, 0);
-    return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
+    return othd::grid_answer(n, [&] { return grid_of(n, 1, 0); });
 }
 
 }  // extern "C"

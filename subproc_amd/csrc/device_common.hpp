@@ -8,7 +8,8 @@
 //     [depth][field][lane] in 32-bit words, so a wave's access is one word per
 //     bank whatever depth each lane is at.  9 words: search_core.hpp's frame,
 //     7: solve_core.hpp's;
-//   * kRefillMin, status_of(), env_int(), ResidentBlocks.
+//   * kRefillMin, status_of(), env_int(), ResidentBlocks, and the grid sizing
+//     of every launch: launch_grid(), grid_answer().
 // Everything device-side is force-inlined: no kernel gets a symbol from here.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -138,5 +139,28 @@ struct ResidentBlocks {
         return r;
     }
 };
+
+// blocks to launch for `items` work items in blocks of `block` lanes: no more
+// than the kernel's resident blocks, than the environment variable `env` says
+// (the tools' A/B) or than the items need.  at_least_one: an empty launch still
+// runs one block (the split files).  <= 0: the current device is out of range.
+inline int launch_grid(ResidentBlocks& cache, const void* kernel, int block, int64_t items, const char* env,
+                       bool at_least_one = false) {
+    const int resident = cache.get(kernel, block);
+    if (resident <= 0) return -1;
+    const int cap = std::min(std::max(env_int(env, resident), 1), resident);
+    const int64_t need = (items + block - 1) / block;
+    return (int)std::min<int64_t>(at_least_one ? std::max<int64_t>(need, 1) : need, (int64_t)cap);
+}
+
+// what a *_grid export answers for n items: OTH_EINVAL below 0, 0 for none
+// (nothing asks the device), else grid(), or an error where that found none
+template <class Grid>
+inline int grid_answer(int64_t n, Grid grid) {
+    if (n < 0) return OTH_EINVAL;
+    if (n == 0) return 0;
+    const int g = grid();
+    return g > 0 ? g : status_of(hipErrorInvalidDevice);
+}
 
 }  // namespace othd

@@ -37,7 +37,6 @@ static_assert(OTHA_SEARCH_SLOTS == 64, "a task per square at most");
 namespace {
 
 using othd::DeviceRules;
-using othd::env_int;
 using othd::kRefillMin;
 using othd::status_of;
 using othd::u32;
@@ -506,12 +505,12 @@ int otha_search_moves(const uint64_t* boards, const uint8_t* turn, int depth, co
         (n > 0 && (!boards || !scratch || ((uintptr_t)scratch & 15) || scratch_bytes < need)))
         return OTH_EINVAL;
     if (n == 0) return OTH_OK;
-    const int resident = g_resident.get(reinterpret_cast<const void*>(search_moves_kernel), kSearchBlock);
-    if (resident <= 0) return status_of(hipErrorInvalidDevice);
     // the task count is the device's: a wave per 8 positions' worth of lanes
     // (about 8 moves each), capped like othm_search's grid
-    const int cap = std::min(std::max(env_int("OTH_SEARCH_BLOCKS", resident), 1), resident);
-    const int grid = (int)std::min<int64_t>((n + 7) / 8, (int64_t)cap);
+    static_assert(kSearchBlock % 8 == 0, "a block per 8 positions");
+    const int grid = othd::launch_grid(g_resident, reinterpret_cast<const void*>(search_moves_kernel), kSearchBlock,
+                                       n * (kSearchBlock / 8), "OTH_SEARCH_BLOCKS");
+    if (grid <= 0) return status_of(hipErrorInvalidDevice);
     const SearchScratch s = search_scratch(scratch, n);
     hipStream_t q = (hipStream_t)stream;
     int rc = status_of(hipMemsetAsync(s.total, 0, sizeof(*s.total), q));

@@ -37,6 +37,7 @@
 #include "../../include/othello_search.h"
 #include "../../include/othello_order.h"
 #include "device_common.hpp"
+#include "game_out.hpp"
 #include "play_core.hpp"
 
 static_assert(OTHM_MAX_DEPTH == othm::kMaxDepth && OTHM_SEARCHED == othm::kSearched &&
@@ -54,7 +55,6 @@ using othm::u64;
 
 constexpr int kPlayBlock = 64;  // one wave
 using othd::DeviceRules;
-using othd::env_int;
 using othd::kRefillMin;
 using othd::status_of;
 using LdsStack = othd::LdsStack9<kPlayBlock>;
@@ -80,36 +80,9 @@ struct PlayArgs {
     int8_t w[2][OTH_EVAL_WEIGHTS];  // A's table, B's table
 };
 
-// a game's move record: the row starts 255-padded, a move is one byte store
-struct MoveRecord {
-    uint8_t* row;  // NULL: no record
-    __device__ __forceinline__ void pad() const {
-        if (!row) return;
-#pragma unroll
-        for (int q = 0; q < OTH_MOVES_STRIDE / 16; q++) reinterpret_cast<uint4*>(row)[q] = make_uint4(~0u, ~0u, ~0u, ~0u);
-    }
-    __device__ __forceinline__ void move(u32 ply, u32 code) const {
-        if (row && ply < (u32)OTH_MOVES_STRIDE) row[ply] = (uint8_t)code;
-    }
-};
-
-// game g has ended (G.status says how): its outputs, and the histogram's bins
-// if it was played to its end
-__device__ __forceinline__ void emit(const PlayArgs& a, u64 g, const othp::Game& G) {
-    const u64 bl = othp::black_of(G), wh = othp::white_of(G);
-    const int d = G.status == othm::kInvalid ? 0 : __popcll(bl) - __popcll(wh);
-    if (a.a_black) a.a_black[g] = (uint8_t)G.a_black;
-    if (a.final_boards) reinterpret_cast<ulonglong2*>(a.final_boards)[g] = make_ulonglong2(bl, wh);
-    if (a.diff) a.diff[g] = (int8_t)d;
-    if (a.plies) a.plies[g] = (uint8_t)G.ply;
-    if (a.status) a.status[g] = (uint8_t)G.status;
-    if (a.nodes) a.nodes[g] = G.nodes;
-    if (a.hist && G.status == othm::kSearched) {
-        atomicAdd(&a.hist[d + 64], 1ull);
-        atomicAdd(&a.hist[d > 0 ? 129 : (d < 0 ? 130 : 131)], 1ull);
-        atomicAdd(&a.hist[132], (unsigned long long)G.ply);
-    }
-}
+// the game's move record and its outputs: game_out.hpp
+using othp::emit;
+using othp::MoveRecord;
 
 // the persistent loop of both kernels; kOrdered: order_core.hpp's machine
 template <bool kOrdered>
@@ -181,17 +154,10 @@ __global__ __launch_bounds__(kPlayBlock) void play_ordered_kernel(PlayArgs a) { 
 // one cache for play_kernel (order 0), one for the ordered kernel (1)
 othd::ResidentBlocks g_resident[2];
 
-int resident_blocks(int order) {
+int play_grid(int64_t n, int order) {
     const void* kernel = order ? reinterpret_cast<const void*>(play_ordered_kernel)
                                : reinterpret_cast<const void*>(play_kernel);
-    return g_resident[order].get(kernel, kPlayBlock);
-}
-
-int play_grid(int64_t n, int order) {
-    const int resident = resident_blocks(order);
-    if (resident <= 0) return -1;
-    const int cap = std::min(std::max(env_int("OTH_PLAY_BLOCKS", resident), 1), resident);
-    return (int)std::min<int64_t>((n + kPlayBlock - 1) / kPlayBlock, (int64_t)cap);
+    return othd::launch_grid(g_resident[order], kernel, kPlayBlock, n, "OTH_PLAY_BLOCKS");
 }
 
 }  // namespace
@@ -255,10 +221,8 @@ int othp_play(const uint64_t* start, const uint8_t* start_turn, uint64_t seed, u
 }
 
 int otho_play_ordered_grid(int64_t n, int order) {
-    if (order < 0 || order > OTHO_MAX_ORDER || n < 0) return OTH_EINVAL;
-    if (n == 0) return 0;
-    const int grid = play_grid(n, order);
-    return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
+    if (order < 0 || order > OTHO_MAX_ORDER) return OTH_EINVAL;
+    return othd::grid_answer(n, [&] { return play_grid(n, order); });
 }
 
 int othp_play_grid(int64_t n) { return otho_play_ordered_grid(n, 0); }

@@ -44,7 +44,6 @@ using othm::u64;
 
 constexpr int kSearchBlock = 64;  // one wave
 using othd::DeviceRules;
-using othd::env_int;
 using othd::kRefillMin;
 using othd::status_of;
 using LdsStack = othd::LdsStack9<kSearchBlock>;
@@ -134,17 +133,10 @@ __global__ __launch_bounds__(kSearchBlock) void search_ordered_kernel(SearchArgs
 // one cache for search_kernel (order 0), one for the ordered kernel (1)
 othd::ResidentBlocks g_resident[2];
 
-int resident_blocks(int order) {
+int search_grid(int64_t n, int order) {
     const void* kernel = order ? reinterpret_cast<const void*>(search_ordered_kernel)
                                : reinterpret_cast<const void*>(search_kernel);
-    return g_resident[order].get(kernel, kSearchBlock);
-}
-
-int search_grid(int64_t n, int order) {
-    const int resident = resident_blocks(order);
-    if (resident <= 0) return -1;
-    const int cap = std::min(std::max(env_int("OTH_SEARCH_BLOCKS", resident), 1), resident);
-    return (int)std::min<int64_t>((n + kSearchBlock - 1) / kSearchBlock, (int64_t)cap);
+    return othd::launch_grid(g_resident[order], kernel, kSearchBlock, n, "OTH_SEARCH_BLOCKS");
 }
 
 }  // namespace
@@ -187,10 +179,8 @@ int othm_search(const uint64_t* boards, const uint8_t* turn, int depth, const in
 }
 
 int otho_search_ordered_grid(int64_t n, int order) {
-    if (order < 0 || order > OTHO_MAX_ORDER || n < 0) return OTH_EINVAL;
-    if (n == 0) return 0;
-    const int grid = search_grid(n, order);
-    return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
+    if (order < 0 || order > OTHO_MAX_ORDER) return OTH_EINVAL;
+    return othd::grid_answer(n, [&] { return search_grid(n, order); });
 }
 
 int othm_search_grid(int64_t n) { return otho_search_ordered_grid(n, 0); }

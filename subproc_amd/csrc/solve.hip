@@ -189,10 +189,7 @@ othd::ResidentBlocks g_resident[2];  // oths_solve's kernel, othw_solve's
 int solve_grid(int64_t n, bool window = false) {
     const void* kernel = window ? reinterpret_cast<const void*>(solve_windowed)
                                 : reinterpret_cast<const void*>(solve_kernel);
-    const int resident = g_resident[window ? 1 : 0].get(kernel, kSolveBlock);
-    if (resident <= 0) return -1;
-    const int cap = std::min(std::max(env_int("OTH_SOLVE_BLOCKS", resident), 1), resident);
-    return (int)std::min<int64_t>((n + kSolveBlock - 1) / kSolveBlock, (int64_t)cap);
+    return othd::launch_grid(g_resident[window ? 1 : 0], kernel, kSolveBlock, n, "OTH_SOLVE_BLOCKS");
 }
 
 template <bool kWindow>
@@ -245,10 +242,7 @@ int othw_solve(const uint64_t* boards, const uint8_t* turn, const int8_t* alpha,
 }
 
 int oths_solve_grid(int64_t n) {
-    if (n < 0) return OTH_EINVAL;
-    if (n == 0) return 0;
-    const int grid = solve_grid(n);
-    return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
+    return othd::grid_answer(n, [&] { return solve_grid(n); });
 }
 
 }  // extern "C"

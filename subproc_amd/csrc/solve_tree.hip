@@ -66,7 +66,6 @@ constexpr bool kShareBounds = true;
 
 using othd::DeviceAtomics;
 using othd::DeviceRules;
-using othd::env_int;
 using othd::kRefillMin;
 using othd::status_of;
 using LdsStack = othd::LdsStack7<kTaskBlock>;
@@ -671,7 +670,7 @@ __global__ __launch_bounds__(kTaskBlock) void split_window_tasks(TaskArgs a, oth
 // two for their hashed twins, four for the kernels under a root window
 othd::ResidentBlocks g_resident[8];
 
-int resident_blocks(int order, bool hashed, bool windowed) {
+int task_grid(int64_t tasks, int order, bool hashed = false, bool windowed = false) {
     const void* kernel =
         windowed ? (hashed ? (order ? reinterpret_cast<const void*>(split_window_tasks<true, true>)
                                     : reinterpret_cast<const void*>(split_window_tasks<false, true>))
@@ -681,14 +680,8 @@ int resident_blocks(int order, bool hashed, bool windowed) {
                           : reinterpret_cast<const void*>(split_solve_tasks_hashed<false>))
                  : (order ? reinterpret_cast<const void*>(split_solve_tasks_ordered)
                           : reinterpret_cast<const void*>(split_solve_tasks));
-    return g_resident[order + (hashed ? 2 : 0) + (windowed ? 4 : 0)].get(kernel, kTaskBlock);
-}
-
-int task_grid(int64_t tasks, int order, bool hashed = false, bool windowed = false) {
-    const int resident = resident_blocks(order, hashed, windowed);
-    if (resident <= 0) return -1;
-    const int cap = std::min(std::max(env_int("OTH_SOLVE_BLOCKS", resident), 1), resident);
-    return (int)std::min<int64_t>(std::max<int64_t>((tasks + kTaskBlock - 1) / kTaskBlock, 1), (int64_t)cap);
+    return othd::launch_grid(g_resident[order + (hashed ? 2 : 0) + (windowed ? 4 : 0)], kernel, kTaskBlock, tasks,
+                             "OTH_SOLVE_BLOCKS", true);
 }
 
 // n * npp, or -1 when the scratch would not fit 2^62 bytes
@@ -824,10 +817,7 @@ int othw_solve_split(const uint64_t* boards, const uint8_t* turn, int max_emptie
 }
 
 int othe_solve_grid(int64_t tasks) {
-    if (tasks < 0) return OTH_EINVAL;
-    if (tasks == 0) return 0;
-    const int grid = task_grid(tasks, 0);
-    return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
+    return othd::grid_answer(tasks, [&] { return task_grid(tasks, 0); });
 }
 
 }  // extern "C"

@@ -51,7 +51,6 @@ constexpr bool kShareBounds = true;
 
 using othd::DeviceAtomics;
 using othd::DeviceRules;
-using othd::env_int;
 using othd::kRefillMin;
 using othd::status_of;
 using LdsStack = othd::LdsStack9<kTaskBlock>;
@@ -433,17 +432,10 @@ __global__ __launch_bounds__(kTaskBlock) void task_ordered_kernel(TaskArgs a) {
 // one cache for task_kernel (order 0), one for the ordered kernel (1)
 othd::ResidentBlocks g_resident[2];
 
-int resident_blocks(int order) {
+int task_grid(int64_t tasks, int order) {
     const void* kernel = order ? reinterpret_cast<const void*>(task_ordered_kernel)
                                : reinterpret_cast<const void*>(task_kernel);
-    return g_resident[order].get(kernel, kTaskBlock);
-}
-
-int task_grid(int64_t tasks, int order) {
-    const int resident = resident_blocks(order);
-    if (resident <= 0) return -1;
-    const int cap = std::min(std::max(env_int("OTH_SEARCH_BLOCKS", resident), 1), resident);
-    return (int)std::min<int64_t>(std::max<int64_t>((tasks + kTaskBlock - 1) / kTaskBlock, 1), (int64_t)cap);
+    return othd::launch_grid(g_resident[order], kernel, kTaskBlock, tasks, "OTH_SEARCH_BLOCKS", true);
 }
 
 // n * npp, or -1 when the scratch would not fit 2^62 bytes
@@ -520,10 +512,8 @@ int otht_search(const uint64_t* boards, const uint8_t* turn, int depth, int spli
 }
 
 int otho_tree_ordered_grid(int64_t tasks, int order) {
-    if (order < 0 || order > OTHO_MAX_ORDER || tasks < 0) return OTH_EINVAL;
-    if (tasks == 0) return 0;
-    const int grid = task_grid(tasks, order);
-    return grid > 0 ? grid : status_of(hipErrorInvalidDevice);
+    if (order < 0 || order > OTHO_MAX_ORDER) return OTH_EINVAL;
+    return othd::grid_answer(tasks, [&] { return task_grid(tasks, order); });
 }
 
 int otht_search_grid(int64_t tasks) { return otho_tree_ordered_grid(tasks, 0); }

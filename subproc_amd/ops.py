@@ -189,6 +189,59 @@ def work_word(device=None):
     return w
 
 
+# The work-word launch protocol, stated once for every entry point that takes
+# ``work``: _capturing refuses a missing word under capture, _work_ptr chooses
+# the word, _launch makes the call and cleans up after a failed one.
+def _capturing(name, work):
+    """Whether the current stream is capturing; a capture without ``work`` raises."""
+    capturing = torch.cuda.is_current_stream_capturing()
+    if work is None and capturing:
+        raise RuntimeError(f"ops.{name} under graph capture needs an explicit work word: an int64 (1,) device "
+                           "tensor zeroed before the capture, one per captured launch")
+    return capturing
+
+
+def _work_ptr(work, d):
+    """Address of the launch's work word: the caller's, else the current stream's."""
+    return _dev(work_word(d) if work is None else work, "work", torch.int64, (1,), d)
+
+
+def _drop_word(d, stream):
+    """Forget the cached word of (d, stream): the next work_word makes a fresh zeroed one."""
+    _WORK.pop((d.index, stream), None)
+
+
+def _launch(what, fn, args, w, d):
+    """``fn(*args, stream)`` on torch's current stream of device ``d``, then
+    check(); ``w`` is the caller's ``work`` (None: the stream's word).  A failed
+    launch leaves the counter unknown (include/othello.h): the stream's default
+    word is dropped; a caller's word is reset eagerly, never as a captured node."""
+    with torch.cuda.device(d):
+        rc = fn(*args, _stream())
+        if rc != _lib.OTH_OK:
+            if w is None:
+                _drop_word(d, _stream())
+            elif not torch.cuda.is_current_stream_capturing():
+                w.zero_()
+        check(rc, what)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _outputs(n, dtype, want_nodes, d):
+    """The value / best_move / status / nodes tensors of the solves and searches."""
+    return (torch.empty(n, dtype=dtype, device=d), torch.empty(n, dtype=torch.uint8, device=d),
+            torch.empty(n, dtype=torch.uint8, device=d),
+            torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None)
+
+
+def _check32(name, x, lo=0):
+    if not lo <= x < lo + 2**32:
+        raise ValueError(f"{name} must fit 32 bits")
+
+
 def rollout(n, seed, game_id0=0, policy="random", n_random=10, start=None, start_turn=None, record_moves=False,
             hist=None, device="cuda", want_boards=True, want_diff=True, want_plies=True, weights=None,
             weights_white=None, work=None):
@@ -214,10 +267,7 @@ def rollout(n, seed, game_id0=0, policy="random", n_random=10, start=None, start
     """
     if policy not in _POLICIES:
         raise ValueError(f"policy must be 'random', 'greedy' or 'eval', got {policy!r}")
-    capturing = torch.cuda.is_current_stream_capturing()
-    if work is None and capturing:
-        raise RuntimeError("ops.rollout under graph capture needs an explicit work word: an int64 (1,) device "
-                           "tensor zeroed before the capture, one per captured launch")
+    _capturing("rollout", work)
     d = _device(device) if start is None else start.device
     ps = pst = None
     if start is not None:
@@ -234,34 +284,17 @@ def rollout(n, seed, game_id0=0, policy="random", n_random=10, start=None, start
     ph = _dev(hist, "hist", torch.int64, (HIST_BINS,), d)
     if _POLICIES[policy] != POLICY_EVAL and (weights is not None or weights_white is not None):
         raise ValueError("weights apply to policy 'eval' only")
-    w = work_word(d) if work is None else work
-    pw = _dev(w, "work", torch.int64, (1,), d)
-
-    def ptr(t):
-        return None if t is None else t.data_ptr()
-
-    with torch.cuda.device(d):
-        seed64 = seed & (2**64 - 1)
-        if _POLICIES[policy] == POLICY_EVAL and weights_white is not None:
-            rc, what = _lib.load().oth_rollout_match(ps, pst, seed64, game_id0, n_random, _weights_ptr(weights),
-                                                     _weights_ptr(weights_white), ptr(fb), ptr(df), ptr(pl), ptr(mv),
-                                                     ph, pw, n, _stream()), "oth_rollout_match"
-        elif _POLICIES[policy] == POLICY_EVAL:
-            rc, what = _lib.load().oth_rollout_eval(ps, pst, seed64, game_id0, n_random, _weights_ptr(weights),
-                                                    ptr(fb), ptr(df), ptr(pl), ptr(mv), ph, pw, n,
-                                                    _stream()), "oth_rollout_eval"
-        else:
-            rc, what = _lib.load().oth_rollout(ps, pst, seed64, game_id0, _POLICIES[policy], n_random, ptr(fb),
-                                               ptr(df), ptr(pl), ptr(mv), ph, pw, n, _stream()), "oth_rollout"
-        if rc != _lib.OTH_OK:
-            # a failed launch leaves the counter unknown (include/othello.h): the
-            # stream's default word is dropped (the next call makes a fresh zeroed
-            # one); a caller's word is reset eagerly, never as a captured node
-            if work is None:
-                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
-            elif not capturing:
-                w.zero_()
-        check(rc, what)
+    pw = _work_ptr(work, d)
+    lib = _lib.load()
+    if _POLICIES[policy] == POLICY_EVAL and weights_white is not None:
+        fn, what, how = lib.oth_rollout_match, "oth_rollout_match", (n_random, _weights_ptr(weights),
+                                                                     _weights_ptr(weights_white))
+    elif _POLICIES[policy] == POLICY_EVAL:
+        fn, what, how = lib.oth_rollout_eval, "oth_rollout_eval", (n_random, _weights_ptr(weights))
+    else:
+        fn, what, how = lib.oth_rollout, "oth_rollout", (_POLICIES[policy], n_random)
+    _launch(what, fn, (ps, pst, seed & (2**64 - 1), game_id0, *how, _ptr(fb), _ptr(df), _ptr(pl), _ptr(mv), ph, pw, n),
+            work, d)
     return RolloutResult(fb, df, pl, mv, hist)
 
 
@@ -348,7 +381,7 @@ def rollout_batches(n, steps, seed, game_id0=0, policy="random", n_random=10, hi
                 rc = lib.oth_rollout(None, None, seed & (2**64 - 1), g0, pid, n_random, part(fb, 2), part(df),
                                      part(pl), None, ph, w.data_ptr(), m, st.cuda_stream)
             if rc != _lib.OTH_OK:  # the failed launch's word is unknown: drop it (ops.rollout does the same)
-                _WORK.pop((d.index, st.cuda_stream), None)
+                _drop_word(d, st.cuda_stream)
             check(rc, "oth_rollout (rollout_batches launch %d)" % L)
         for st in side:  # the caller's stream waits for every launch
             e = torch.cuda.Event()
@@ -377,8 +410,7 @@ def rollout_runner(n, seed, game_id0=0, policy="eval", weights_a=None, weights_b
     played Black; diff / hist / final boards are by colour."""
     if policy not in ("greedy", "eval"):
         raise ValueError(f"policy must be 'greedy' or 'eval', got {policy!r}")
-    if work is None and torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("ops.rollout_runner under graph capture needs an explicit work word")
+    _capturing("rollout_runner", work)
     d = _device(device) if start is None else start.device
     ps = pst = None
     if start is not None:
@@ -394,20 +426,11 @@ def rollout_runner(n, seed, game_id0=0, policy="eval", weights_a=None, weights_b
     if hist is None:
         hist = torch.zeros(HIST_BINS, dtype=torch.int64, device=d)
     ph = _dev(hist, "hist", torch.int64, (HIST_BINS,), d)
-    w = work_word(d) if work is None else work
-    pw = _dev(w, "work", torch.int64, (1,), d)
-    with torch.cuda.device(d):
-        rc = _lib.load().oth_rollout_runner(ps, pst, seed & (2**64 - 1), game_id0, _POLICIES[policy],
-                                            _weights_ptr(weights_a), _weights_ptr(weights_b), int(n_rand_a),
-                                            int(n_rand_b), int(bool(swap_colours)), ab.data_ptr(), fb.data_ptr(),
-                                            df.data_ptr(), pl.data_ptr(), None if mv is None else mv.data_ptr(), ph,
-                                            pw, n, _stream())
-        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
-            if work is None:
-                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
-            elif not torch.cuda.is_current_stream_capturing():
-                w.zero_()
-        check(rc, "oth_rollout_runner")
+    pw = _work_ptr(work, d)
+    _launch("oth_rollout_runner", _lib.load().oth_rollout_runner,
+            (ps, pst, seed & (2**64 - 1), game_id0, _POLICIES[policy], _weights_ptr(weights_a), _weights_ptr(weights_b),
+             int(n_rand_a), int(n_rand_b), int(bool(swap_colours)), ab.data_ptr(), fb.data_ptr(), df.data_ptr(),
+             pl.data_ptr(), _ptr(mv), ph, pw, n), work, d)
     return RunnerResult(fb, df, pl, mv, hist, ab)
 
 
@@ -436,6 +459,26 @@ class SolveTable:
 
     def clear(self):
         self.data.zero_()
+
+
+def _check_table(whose, table, task_empties, hash_min_empties, d):
+    """The ``table`` / ``hash_min_empties`` checks of :func:`solve` and :func:`solve_moves`."""
+    if table is None:
+        return
+    if task_empties is None:
+        raise ValueError(f"{whose} table serves the split solver's tasks: table needs task_empties")
+    if not isinstance(table, SolveTable):
+        raise TypeError("table must be an ops.SolveTable")
+    if not _lib.SOLVE_HASH_MIN_EMPTIES_LO <= int(hash_min_empties) <= _lib.SOLVE_HASH_MIN_EMPTIES_HI:
+        raise ValueError(f"hash_min_empties must lie in {_lib.SOLVE_HASH_MIN_EMPTIES_LO}.."
+                         f"{_lib.SOLVE_HASH_MIN_EMPTIES_HI}")
+    if table.device != d:
+        raise ValueError(f"table is on {table.device}, boards on {d}")
+
+
+def _table_args(table, hash_min_empties):
+    """bits, min_empties, table, table_bytes of the C-ABI; no table is 0, 0, NULL, 0."""
+    return (0, 0, None, 0) if table is None else (table.bits, hash_min_empties, table.data.data_ptr(), table.nbytes)
 
 
 def _solve_window(window, wld, n, d):
@@ -534,22 +577,9 @@ def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=Non
     """
     n = _n(boards)
     win = _solve_window(window, bool(wld), n, boards.device)
-    capturing = torch.cuda.is_current_stream_capturing()
-    if work is None and capturing:
-        raise RuntimeError("ops.solve under graph capture needs an explicit work word: an int64 (1,) device "
-                           "tensor zeroed before the capture, one per captured launch")
-    if not 0 <= int(node_limit) < 2**32:
-        raise ValueError("node_limit must fit 32 bits")
-    if table is not None:
-        if task_empties is None:
-            raise ValueError("ops.solve's table serves the split solver's tasks: table needs task_empties")
-        if not isinstance(table, SolveTable):
-            raise TypeError("table must be an ops.SolveTable")
-        if not _lib.SOLVE_HASH_MIN_EMPTIES_LO <= int(hash_min_empties) <= _lib.SOLVE_HASH_MIN_EMPTIES_HI:
-            raise ValueError(f"hash_min_empties must lie in {_lib.SOLVE_HASH_MIN_EMPTIES_LO}.."
-                             f"{_lib.SOLVE_HASH_MIN_EMPTIES_HI}")
-        if table.device != boards.device:
-            raise ValueError(f"table is on {table.device}, boards on {boards.device}")
+    capturing = _capturing("solve", work)
+    _check32("node_limit", int(node_limit))
+    _check_table("ops.solve's", table, task_empties, hash_min_empties, boards.device)
     if task_empties is not None:
         return _solve_split(boards, turn, n, int(max_empties), int(task_empties), int(order), int(node_limit),
                             want_nodes, work, int(nodes_per_position), capturing, table, int(hash_min_empties), win)
@@ -558,27 +588,13 @@ def solve(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=Non
     d = boards.device
     pb = _dev(boards, "boards", torch.int64)
     pt = _dev(turn, "turn", torch.uint8, (n,), d)
-    val = torch.empty(n, dtype=torch.int8, device=d)
-    mv = torch.empty(n, dtype=torch.uint8, device=d)
-    st = torch.empty(n, dtype=torch.uint8, device=d)
-    nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
-    w = work_word(d) if work is None else work
-    pw = _dev(w, "work", torch.int64, (1,), d)
-    with torch.cuda.device(d):
-        out = (int(max_empties), int(node_limit), val.data_ptr(), mv.data_ptr(), st.data_ptr(),
-               None if nd is None else nd.data_ptr(), pw, n, _stream())
-        if win is None:
-            what = "oths_solve"
-            rc = _lib.load().oths_solve(pb, pt, *out)
-        else:
-            what = "othw_solve"
-            rc = _lib.load().othw_solve(pb, pt, *(None if x is None else x.data_ptr() for x in win), *out)
-        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
-            if work is None:
-                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
-            elif not capturing:
-                w.zero_()
-        check(rc, what)
+    val, mv, st, nd = _outputs(n, torch.int8, want_nodes, d)
+    pw = _work_ptr(work, d)
+    out = (int(max_empties), int(node_limit), val.data_ptr(), mv.data_ptr(), st.data_ptr(), _ptr(nd), pw, n)
+    if win is None:
+        _launch("oths_solve", _lib.load().oths_solve, (pb, pt, *out), work, d)
+    else:
+        _launch("othw_solve", _lib.load().othw_solve, (pb, pt, *map(_ptr, win), *out), work, d)
     return SolveResult(val, mv, st, nd)
 
 
@@ -588,8 +604,7 @@ def _solve_split(boards, turn, n, max_empties, task_empties, order, node_limit, 
     (othh_solve_hashed with a table, othw_solve_split with a window)."""
     if capturing:
         raise RuntimeError("ops.solve(task_empties=...) allocates its scratch and does not run under graph capture")
-    if not -2**31 <= nodes_per_position < 2**31:
-        raise ValueError("nodes_per_position must fit 32 bits")
+    _check32("nodes_per_position", nodes_per_position, -2**31)
     d = boards.device
     pb = _dev(boards, "boards", torch.int64)
     pt = _dev(turn, "turn", torch.uint8, (n,), d)
@@ -597,35 +612,17 @@ def _solve_split(boards, turn, n, max_empties, task_empties, order, node_limit, 
     size = lib.othe_scratch_bytes(n, nodes_per_position)
     if size < 0:
         check(int(size), "othe_scratch_bytes")
-    val = torch.empty(n, dtype=torch.int8, device=d)
-    mv = torch.empty(n, dtype=torch.uint8, device=d)
-    st = torch.empty(n, dtype=torch.uint8, device=d)
-    nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
+    val, mv, st, nd = _outputs(n, torch.int8, want_nodes, d)
     scratch = torch.empty(max(int(size), 8) // 8, dtype=torch.int64, device=d)
-    w = work_word(d) if work is None else work
-    pw = _dev(w, "work", torch.int64, (1,), d)
-    with torch.cuda.device(d):
-        args = (pb, pt, max_empties, task_empties, order, node_limit, val.data_ptr(), mv.data_ptr(), st.data_ptr(),
-                None if nd is None else nd.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, nodes_per_position,
-                pw, n)
-        if win is not None:
-            what = "othw_solve_split"
-            tab = (0, 0, None, 0) if table is None else (table.bits, hash_min_empties, table.data.data_ptr(),
-                                                         table.nbytes)
-            rc = lib.othw_solve_split(*args, *(None if x is None else x.data_ptr() for x in win), *tab, _stream())
-        elif table is None:
-            what = "othe_solve"
-            rc = lib.othe_solve(*args, _stream())
-        else:
-            what = "othh_solve_hashed"
-            rc = lib.othh_solve_hashed(*args, table.bits, hash_min_empties, table.data.data_ptr(), table.nbytes,
-                                       _stream())
-        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
-            if work is None:
-                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
-            else:
-                w.zero_()
-        check(rc, what)
+    args = (pb, pt, max_empties, task_empties, order, node_limit, val.data_ptr(), mv.data_ptr(), st.data_ptr(),
+            _ptr(nd), scratch.data_ptr(), scratch.numel() * 8, nodes_per_position, _work_ptr(work, d), n)
+    if win is not None:
+        _launch("othw_solve_split", lib.othw_solve_split,
+                (*args, *map(_ptr, win), *_table_args(table, hash_min_empties)), work, d)
+    elif table is None:
+        _launch("othe_solve", lib.othe_solve, args, work, d)
+    else:
+        _launch("othh_solve_hashed", lib.othh_solve_hashed, (*args, *_table_args(table, hash_min_empties)), work, d)
     # (the caching allocator hands the scratch to later work of THIS stream only)
     return SolveResult(val, mv, st, nd)
 
@@ -674,36 +671,21 @@ def search(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, wo
     searches inside the tasks are ordered, the tree's expansion is not.
     """
     n = _n(boards)
-    capturing = torch.cuda.is_current_stream_capturing()
-    if work is None and capturing:
-        raise RuntimeError("ops.search under graph capture needs an explicit work word: an int64 (1,) device "
-                           "tensor zeroed before the capture, one per captured launch")
-    if not 0 <= int(node_limit) < 2**32:
-        raise ValueError("node_limit must fit 32 bits")
+    capturing = _capturing("search", work)
+    _check32("node_limit", int(node_limit))
     if int(split) != 0:
         return _search_split(boards, turn, n, int(depth), int(split), weights, int(node_limit), want_nodes, work,
                              int(nodes_per_position), capturing, int(order))
     d = boards.device
     pb = _dev(boards, "boards", torch.int64)
     pt = _dev(turn, "turn", torch.uint8, (n,), d)
-    val = torch.empty(n, dtype=torch.int32, device=d)
-    mv = torch.empty(n, dtype=torch.uint8, device=d)
-    st = torch.empty(n, dtype=torch.uint8, device=d)
-    nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
-    w = work_word(d) if work is None else work
-    pw = _dev(w, "work", torch.int64, (1,), d)
+    val, mv, st, nd = _outputs(n, torch.int32, want_nodes, d)
+    pw = _work_ptr(work, d)
     lib = _lib.load()
     fn, name, ordered = (lib.otho_search_ordered, "otho_search_ordered", (int(order),)) if int(order) != 0 else (
         lib.othm_search, "othm_search", ())
-    with torch.cuda.device(d):
-        rc = fn(pb, pt, int(depth), *ordered, _weights_ptr(weights), int(node_limit), val.data_ptr(), mv.data_ptr(),
-                st.data_ptr(), None if nd is None else nd.data_ptr(), pw, n, _stream())
-        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
-            if work is None:
-                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
-            elif not capturing:
-                w.zero_()
-        check(rc, name)
+    _launch(name, fn, (pb, pt, int(depth), *ordered, _weights_ptr(weights), int(node_limit), val.data_ptr(),
+                       mv.data_ptr(), st.data_ptr(), _ptr(nd), pw, n), work, d)
     return SearchResult(val, mv, st, nd)
 
 
@@ -712,8 +694,7 @@ def _search_split(boards, turn, n, depth, split, weights, node_limit, want_nodes
     """:func:`search` with split >= 1: otht_search (otho_tree_ordered with order != 0) on a scratch of its own."""
     if capturing:
         raise RuntimeError("ops.search(split >= 1) allocates its scratch and does not run under graph capture")
-    if not -2**31 <= nodes_per_position < 2**31:
-        raise ValueError("nodes_per_position must fit 32 bits")
+    _check32("nodes_per_position", nodes_per_position, -2**31)
     d = boards.device
     pb = _dev(boards, "boards", torch.int64)
     pt = _dev(turn, "turn", torch.uint8, (n,), d)
@@ -721,25 +702,14 @@ def _search_split(boards, turn, n, depth, split, weights, node_limit, want_nodes
     size = lib.otht_scratch_bytes(n, nodes_per_position)
     if size < 0:
         check(int(size), "otht_scratch_bytes")
-    val = torch.empty(n, dtype=torch.int32, device=d)
-    mv = torch.empty(n, dtype=torch.uint8, device=d)
-    st = torch.empty(n, dtype=torch.uint8, device=d)
-    nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
+    val, mv, st, nd = _outputs(n, torch.int32, want_nodes, d)
     scratch = torch.empty(max(int(size), 8) // 8, dtype=torch.int64, device=d)
-    w = work_word(d) if work is None else work
-    pw = _dev(w, "work", torch.int64, (1,), d)
+    pw = _work_ptr(work, d)
     fn, name, ordered = (lib.otho_tree_ordered, "otho_tree_ordered", (order,)) if order != 0 else (
         lib.otht_search, "otht_search", ())
-    with torch.cuda.device(d):
-        rc = fn(pb, pt, depth, split, *ordered, _weights_ptr(weights), node_limit, val.data_ptr(), mv.data_ptr(),
-                st.data_ptr(), None if nd is None else nd.data_ptr(), scratch.data_ptr(), scratch.numel() * 8,
-                nodes_per_position, pw, n, _stream())
-        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
-            if work is None:
-                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
-            else:
-                w.zero_()
-        check(rc, name)
+    _launch(name, fn, (pb, pt, depth, split, *ordered, _weights_ptr(weights), node_limit, val.data_ptr(),
+                       mv.data_ptr(), st.data_ptr(), _ptr(nd), scratch.data_ptr(), scratch.numel() * 8,
+                       nodes_per_position, pw, n), work, d)
     # (the caching allocator hands the scratch to later work of THIS stream only)
     return SearchResult(val, mv, st, nd)
 
@@ -769,10 +739,7 @@ def search_budget(boards, turn, budget, max_depth=8, weights=None, order=0, want
     d = boards.device
     pb = _dev(boards, "boards", torch.int64)
     pt = _dev(turn, "turn", torch.uint8, (n,), d)
-    capturing = torch.cuda.is_current_stream_capturing()
-    if work is None and capturing:
-        raise RuntimeError("ops.search_budget under graph capture needs an explicit work word: an int64 (1,) device "
-                           "tensor zeroed before the capture, one per captured launch")
+    capturing = _capturing("search_budget", work)
     per_position = None
     if isinstance(budget, torch.Tensor):
         if budget.dtype == torch.int64:
@@ -791,31 +758,19 @@ def search_budget(boards, turn, budget, max_depth=8, weights=None, order=0, want
         scalar, pbud = int(budget), None
         if not 1 <= scalar < 2**32:
             raise ValueError("budget must lie in 1..2**32 - 1")
-    val = torch.empty(n, dtype=torch.int32, device=d)
-    mv = torch.empty(n, dtype=torch.uint8, device=d)
-    st = torch.empty(n, dtype=torch.uint8, device=d)
+    val, mv, st, nd = _outputs(n, torch.int32, want_nodes, d)
     dp = torch.empty(n, dtype=torch.uint8, device=d)
-    nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
-    w = work_word(d) if work is None else work
-    pw = _dev(w, "work", torch.int64, (1,), d)
-    lib = _lib.load()
-    with torch.cuda.device(d):
-        rc = lib.othb_search(pb, pt, int(max_depth), _weights_ptr(weights), scalar, pbud, int(order), val.data_ptr(),
-                             mv.data_ptr(), dp.data_ptr(), st.data_ptr(), None if nd is None else nd.data_ptr(), pw, n,
-                             _stream())
-        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
-            if work is None:
-                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
-            elif not capturing:
-                w.zero_()
-        check(rc, "othb_search")
+    pw = _work_ptr(work, d)
+    _launch("othb_search", _lib.load().othb_search,
+            (pb, pt, int(max_depth), _weights_ptr(weights), scalar, pbud, int(order), val.data_ptr(), mv.data_ptr(),
+             dp.data_ptr(), st.data_ptr(), _ptr(nd), pw, n), work, d)
     return BudgetResult(val, mv, st, dp, nd)
 
 
 MovesResult = namedtuple("MovesResult", "move_value value best_move status nodes")
 
 
-def _moves_call(name, fn, size, head, boards, turn, n, dtype, want_nodes, work, capturing):
+def _moves_call(name, fn, size, head, boards, turn, n, dtype, want_nodes, work):
     """The shared half of :func:`solve_moves` and :func:`search_moves`: the
     outputs, a scratch of ``size`` bytes, the work word, and the call
     ``fn(boards, turn, *head, move_value, value, best_move, status, nodes,
@@ -826,22 +781,10 @@ def _moves_call(name, fn, size, head, boards, turn, n, dtype, want_nodes, work, 
     if size < 0:
         check(int(size), name + "_scratch_bytes")
     rows = torch.empty((n, 64), dtype=dtype, device=d)
-    val = torch.empty(n, dtype=dtype, device=d)
-    mv = torch.empty(n, dtype=torch.uint8, device=d)
-    st = torch.empty(n, dtype=torch.uint8, device=d)
-    nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
+    val, mv, st, nd = _outputs(n, dtype, want_nodes, d)
     scratch = torch.empty(max(int(size), 16) // 8, dtype=torch.int64, device=d)
-    w = work_word(d) if work is None else work
-    pw = _dev(w, "work", torch.int64, (1,), d)
-    with torch.cuda.device(d):
-        rc = fn(pb, pt, *head, rows.data_ptr(), val.data_ptr(), mv.data_ptr(), st.data_ptr(),
-                None if nd is None else nd.data_ptr(), scratch.data_ptr(), scratch.numel() * 8, pw, n, _stream())
-        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
-            if work is None:
-                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
-            elif not capturing:
-                w.zero_()
-        check(rc, name)
+    _launch(name, fn, (pb, pt, *head, rows.data_ptr(), val.data_ptr(), mv.data_ptr(), st.data_ptr(), _ptr(nd),
+                       scratch.data_ptr(), scratch.numel() * 8, _work_ptr(work, d), n), work, d)
     # (the caching allocator hands the scratch to later work of THIS stream only)
     return MovesResult(rows, val, mv, st, nd)
 
@@ -882,41 +825,25 @@ def solve_moves(boards, turn, max_empties=12, node_limit=0, want_nodes=False, wo
     the scratch then belongs to the graph's pool — the split form may not.
     """
     n = _n(boards)
-    if not 0 <= int(node_limit) < 2**32:
-        raise ValueError("node_limit must fit 32 bits")
+    _check32("node_limit", int(node_limit))
     if task_empties is None and int(order) != 0:
         raise ValueError("ops.solve_moves orders moves only inside the split solver's tasks: order needs task_empties")
-    if table is not None:
-        if task_empties is None:
-            raise ValueError("ops.solve_moves' table serves the split solver's tasks: table needs task_empties")
-        if not isinstance(table, SolveTable):
-            raise TypeError("table must be an ops.SolveTable")
-        if not _lib.SOLVE_HASH_MIN_EMPTIES_LO <= int(hash_min_empties) <= _lib.SOLVE_HASH_MIN_EMPTIES_HI:
-            raise ValueError(f"hash_min_empties must lie in {_lib.SOLVE_HASH_MIN_EMPTIES_LO}.."
-                             f"{_lib.SOLVE_HASH_MIN_EMPTIES_HI}")
-        if table.device != boards.device:
-            raise ValueError(f"table is on {table.device}, boards on {boards.device}")
+    _check_table("ops.solve_moves'", table, task_empties, hash_min_empties, boards.device)
     _dev(boards, "boards", torch.int64)  # (a host tensor is refused before anything asks the device)
-    capturing = torch.cuda.is_current_stream_capturing()
-    if work is None and capturing:
-        raise RuntimeError("ops.solve_moves under graph capture needs an explicit work word: an int64 (1,) device "
-                           "tensor zeroed before the capture, one per captured launch")
+    capturing = _capturing("solve_moves", work)
     lib = _lib.load()
     if task_empties is None:
         return _moves_call("otha_solve_moves", lib.otha_solve_moves,
                            lib.otha_solve_moves_scratch_bytes(n, int(max_empties)),
-                           (int(max_empties), int(node_limit)), boards, turn, n, torch.int8, want_nodes, work, capturing)
+                           (int(max_empties), int(node_limit)), boards, turn, n, torch.int8, want_nodes, work)
     if capturing:
         raise RuntimeError("ops.solve_moves(task_empties=...) does not run under graph capture")
     npp = int(nodes_per_position)
-    if not -2**31 <= npp < 2**31:
-        raise ValueError("nodes_per_position must fit 32 bits")
-    tab = (0, 0, None, 0) if table is None else (table.bits, int(hash_min_empties), table.data.data_ptr(),
-                                                 table.nbytes)
+    _check32("nodes_per_position", npp, -2**31)
     return _moves_call("otha_solve_moves_split", lib.otha_solve_moves_split,
                        lib.otha_solve_moves_split_scratch_bytes(n, int(max_empties), npp),
-                       (int(max_empties), int(task_empties), int(order), int(node_limit), npp, *tab), boards, turn, n,
-                       torch.int8, want_nodes, work, capturing)
+                       (int(max_empties), int(task_empties), int(order), int(node_limit), npp,
+                        *_table_args(table, int(hash_min_empties))), boards, turn, n, torch.int8, want_nodes, work)
 
 
 def search_moves(boards, turn, depth, weights=None, node_limit=0, want_nodes=False, work=None):
@@ -942,17 +869,13 @@ def search_moves(boards, turn, depth, weights=None, node_limit=0, want_nodes=Fal
     word.
     """
     n = _n(boards)
-    if not 0 <= int(node_limit) < 2**32:
-        raise ValueError("node_limit must fit 32 bits")
+    _check32("node_limit", int(node_limit))
     _dev(boards, "boards", torch.int64)  # (a host tensor is refused before anything asks the device)
-    capturing = torch.cuda.is_current_stream_capturing()
-    if work is None and capturing:
-        raise RuntimeError("ops.search_moves under graph capture needs an explicit work word: an int64 (1,) device "
-                           "tensor zeroed before the capture, one per captured launch")
+    _capturing("search_moves", work)
     lib = _lib.load()
     return _moves_call("otha_search_moves", lib.otha_search_moves, lib.otha_search_moves_scratch_bytes(n),
                        (int(depth), _weights_ptr(weights), int(node_limit)), boards, turn, n, torch.int32, want_nodes,
-                       work, capturing)
+                       work)
 
 
 PlayResult = namedtuple("PlayResult", "final_boards diff plies moves hist a_black status nodes")
@@ -996,12 +919,8 @@ def play(n, seed, game_id0=0, weights_a=None, weights_b=None, depth_a=1, depth_b
         budgets = (int(budget),) * 2 if isinstance(budget, numbers.Integral) else tuple(int(b) for b in budget)
         if len(budgets) != 2 or not all(1 <= b < 2**32 for b in budgets):
             raise ValueError("budget must be an int or a pair (Ba, Bb) of ints in 1..2**32 - 1")
-    capturing = torch.cuda.is_current_stream_capturing()
-    if work is None and capturing:
-        raise RuntimeError("ops.play under graph capture needs an explicit work word: an int64 (1,) device "
-                           "tensor zeroed before the capture, one per captured launch")
-    if not 0 <= int(node_limit) < 2**32:
-        raise ValueError("node_limit must fit 32 bits")
+    _capturing("play", work)
+    _check32("node_limit", int(node_limit))
     d = _device(device) if start is None else start.device
     ps = pst = None
     if start is not None:
@@ -1019,25 +938,17 @@ def play(n, seed, game_id0=0, weights_a=None, weights_b=None, depth_a=1, depth_b
     if hist is None:
         hist = torch.zeros(HIST_BINS, dtype=torch.int64, device=d)
     ph = _dev(hist, "hist", torch.int64, (HIST_BINS,), d)
-    w = work_word(d) if work is None else work
-    pw = _dev(w, "work", torch.int64, (1,), d)
+    pw = _work_ptr(work, d)
     lib = _lib.load()
     fn, name, ordered = (lib.otho_play_ordered, "otho_play_ordered", (int(order),)) if int(order) != 0 else (
         lib.othp_play, "othp_play", ())
     if budgets:
         fn, name, ordered = lib.othb_play, "othb_play", (int(order),)
-    with torch.cuda.device(d):
-        rc = fn(ps, pst, seed & (2**64 - 1), game_id0, _weights_ptr(weights_a), _weights_ptr(weights_b), int(depth_a),
-                int(depth_a if depth_b is None else depth_b), *budgets, int(exact_empties), *ordered, int(n_rand_a),
-                int(n_rand_b), int(bool(swap_colours)), int(node_limit), ab.data_ptr(), fb.data_ptr(), df.data_ptr(),
-                pl.data_ptr(), None if mv is None else mv.data_ptr(), st.data_ptr(),
-                None if nd is None else nd.data_ptr(), ph, pw, n, _stream())
-        if rc != _lib.OTH_OK:  # as ops.rollout: drop the stream's default word, reset a caller's eagerly
-            if work is None:
-                _WORK.pop((d.index, torch.cuda.current_stream().cuda_stream), None)
-            elif not capturing:
-                w.zero_()
-        check(rc, name)
+    _launch(name, fn, (ps, pst, seed & (2**64 - 1), game_id0, _weights_ptr(weights_a), _weights_ptr(weights_b),
+                       int(depth_a), int(depth_a if depth_b is None else depth_b), *budgets, int(exact_empties),
+                       *ordered, int(n_rand_a), int(n_rand_b), int(bool(swap_colours)), int(node_limit), ab.data_ptr(),
+                       fb.data_ptr(), df.data_ptr(), pl.data_ptr(), _ptr(mv), st.data_ptr(), _ptr(nd), ph, pw, n),
+            work, d)
     return PlayResult(fb, df, pl, mv, hist, ab, st, nd)
 
 

@@ -10,10 +10,10 @@ import subprocess
 
 import pytest
 
+import codeobj
 from subproc_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
 OTHERS = ("oth", "oths", "othm", "othp", "otht", "otho", "othe", "othh", "othw", "otha")
 NAMES = ["othb_play", "othb_play_grid", "othb_search", "othb_search_grid"]
 
@@ -117,37 +117,12 @@ def test_python_layers_refuse_bad_arguments_before_they_touch_a_device():
     assert out == [runner.hamlet_param_line("H", "search", w, 6, 0, 512)]
 
 
-def kernel_resources(tmp_path, wanted):
-    """name -> resources of the gfx950 kernels whose name holds one of `wanted`"""
-    fb = str(tmp_path / "fb.bin")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, _lib.LIB_PATH,
-                           str(tmp_path / "host.so")])
-    blob = open(fb, "rb").read()
-    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)] + [len(blob)]
-    found = {}
-    for i in range(len(starts) - 1):
-        part, co = str(tmp_path / f"fb{i}.bin"), str(tmp_path / f"co{i}.o")
-        open(part, "wb").write(blob[starts[i]:starts[i + 1]])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-        notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
-        for block in notes.split("- .agpr_count")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", block).group(1)
-            if any(k in name for k in wanted):
-                found[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
-                               for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count",
-                                         "sgpr_count")}
-    return found
-
-
-def test_the_budget_kernels_use_no_scratch_and_keep_the_searchs_and_the_games_footprint(tmp_path):
+def test_the_budget_kernels_use_no_scratch_and_keep_the_searchs_and_the_games_footprint():
     """One-wave blocks with the frames and the widened table(s) in LDS
     (7 x 9 x 64 words + 48 ints, or + 96): search.hip's and play.hip's
     footprint, so eight blocks a CU; registers for two waves per SIMD.
     DESIGN.md §22 has the figures."""
-    if not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("ROCm LLVM tools not present")
-    found = kernel_resources(tmp_path, ("budget_deepen", "budget_play", "13search_kernel", "11play_kernel"))
+    found = codeobj.named(("budget_deepen", "budget_play", "13search_kernel", "11play_kernel"))
     new = {n: k for n, k in found.items() if "budget_" in n}
     assert len(new) == 4 and len(found) == 6, sorted(found)  # search and games, unordered and ordered; the two models
     for name, k in new.items():

@@ -9,38 +9,7 @@ notes of the device code, runs nothing on a GPU).
 * The random rollout kernel fits 6 waves per SIMD (<= 85 VGPRs): the bench's
   two launches in flight sit side by side at 3 blocks per CU.
 """
-import os
-import re
-import subprocess
-
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "subproc_amd", "lib", "libsubproc_amd_hip.so")
-LLVM = "/opt/rocm/lib/llvm/bin"
-
-
-def kernel_notes(tmp_path):
-    if not os.path.exists(LIB):
-        pytest.skip("HIP library not built (__graft_entry__.build())")
-    if not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("ROCm LLVM tools not present")
-    fb, co = str(tmp_path / "fb.bin"), str(tmp_path / "co.o")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, LIB,
-                           str(tmp_path / "host.so")])
-    subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + fb,
-                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-    notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
-    kernels, cur = {}, None
-    for ln in notes.splitlines():
-        m = re.match(r"\s+\.name:\s+(\S+)", ln)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.match(r"\s+\.(private_segment_fixed_size|vgpr_count):\s+(\d+)", ln)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    return kernels
+import codeobj
 
 
 # The one known exception (round 5): the eval-policy rollout kernels hold their
@@ -57,20 +26,27 @@ def kernel_notes(tmp_path):
 # gpu_greedy_ab.sh): 3.239e10 against 3.198e10 env-steps/s at two streams,
 # 2.116 against 2.140 ms per one-stream launch; the scratch adds 16.8 MB of
 # HBM writes per 1M-game launch (37.4 against 20.6 MB), 10 GB/s.
-SCRATCH_ALLOWED = {"rollout_kernelILi2E": 32, "rollout_kernelILi1E": 68}
+# rocprim's trampoline_kernel (four radix-sort instances, 48 B each) is library
+# code in td_table.hip's bundle, not ours.
+SCRATCH_ALLOWED = {"rollout_kernelILi2E": 32, "rollout_kernelILi1E": 68, "6detail17trampoline_kernel": 48}
+# one kernel of each of the library's nine bundles (one per .hip file), in
+# __graft_entry__.HIP_SRC's order: the guard below reads every one of them
+ONE_PER_BUNDLE = ("14rollout_kernel", "15td_merge_kernel", "12solve_kernel", "13search_kernel", "11play_kernel",
+                  "11task_kernel", "17split_solve_tasks", "19moves_expand_search", "20budget_deepen_kernel")
 
 
-def test_no_kernel_uses_scratch(tmp_path):
-    k = kernel_notes(tmp_path)
+def test_no_kernel_uses_scratch():
+    k = codeobj.kernels()
     names = " ".join(k)
     assert "rollout_kernel" in names and "replay_kernel" in names and "step_kernel" in names
+    assert all(sub in names for sub in ONE_PER_BUNDLE), [sub for sub in ONE_PER_BUNDLE if sub not in names]
     spilled = {n: v["private_segment_fixed_size"] for n, v in k.items() if v.get("private_segment_fixed_size")}
     allowed = {n: b for n, b in spilled.items() if any(p in n and b <= cap for p, cap in SCRATCH_ALLOWED.items())}
     assert not set(spilled) - set(allowed), f"kernels with scratch: {spilled}"
 
 
-def test_random_rollout_fits_six_waves(tmp_path):
-    k = kernel_notes(tmp_path)
+def test_random_rollout_fits_six_waves():
+    k = codeobj.kernels()
     rnd = [v for n, v in k.items() if "rollout_kernelILi0ELb0ELb0E" in n]
     assert len(rnd) == 1
     assert rnd[0]["vgpr_count"] <= 85, rnd[0]

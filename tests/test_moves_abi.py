@@ -10,10 +10,10 @@ import subprocess
 
 import pytest
 
+import codeobj
 from subproc_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
 OTHERS = ("oth", "oths", "othm", "othp", "otht", "otho", "othe", "othh", "othw")
 NAMES = ["otha_search_moves", "otha_search_moves_scratch_bytes", "otha_solve_moves", "otha_solve_moves_scratch_bytes",
          "otha_solve_moves_split", "otha_solve_moves_split_scratch_bytes"]
@@ -151,37 +151,12 @@ def test_python_layers_refuse_bad_arguments_before_they_touch_a_device():
     assert callable(engine.Engine.hint)
 
 
-def kernel_resources(tmp_path, wanted):
-    """name -> resources of the gfx950 kernels whose name holds one of `wanted`"""
-    fb = str(tmp_path / "fb.bin")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, _lib.LIB_PATH,
-                           str(tmp_path / "host.so")])
-    blob = open(fb, "rb").read()
-    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)] + [len(blob)]
-    found = {}
-    for i in range(len(starts) - 1):
-        part, co = str(tmp_path / f"fb{i}.bin"), str(tmp_path / f"co{i}.o")
-        open(part, "wb").write(blob[starts[i]:starts[i + 1]])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-        notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
-        for block in notes.split("- .agpr_count")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", block).group(1)
-            if any(k in name for k in wanted):
-                found[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
-                               for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count",
-                                         "sgpr_count")}
-    return found
-
-
-def test_the_new_kernels_use_no_scratch_and_keep_the_searchs_footprint(tmp_path):
+def test_the_new_kernels_use_no_scratch_and_keep_the_searchs_footprint():
     """search_moves_kernel is search.hip's loop: one-wave blocks, the frames
     and the widened table in LDS (7 x 9 x 64 words + 48 ints), registers for
     two waves per SIMD.  The expand and finish kernels use neither LDS nor
     scratch.  DESIGN.md §21 has the figures."""
-    if not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("ROCm LLVM tools not present")
-    found = kernel_resources(tmp_path, ("moves_expand", "moves_finish", "search_moves_kernel"))
+    found = codeobj.named(("moves_expand", "moves_finish", "search_moves_kernel"))
     assert len(found) == 5, sorted(found)  # two expands, the finish for int8 and int32 rows, the search
     for name, k in found.items():
         assert k["private_segment_fixed_size"] == 0, name

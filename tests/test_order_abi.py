@@ -4,17 +4,15 @@ unordered calls reject and every order but 0 and 1 before it touches a device,
 its kernels keep the stack in LDS at the unordered kernels' footprint, and the
 tie cases the GPU tests rely on do exercise the root tie rule (CPU only)."""
 import ctypes
-import os
 import re
 import subprocess
 
 import numpy as np
-import pytest
 
+import codeobj
 import order_cases
 from subproc_amd import _lib, params
 
-LLVM = "/opt/rocm/lib/llvm/bin"
 EINVAL = _lib.OTH_EINVAL
 NAMES = ["otho_play_ordered", "otho_play_ordered_grid", "otho_search_ordered", "otho_search_ordered_grid",
          "otho_tree_ordered", "otho_tree_ordered_grid"]
@@ -112,35 +110,12 @@ def test_bad_orders_and_bad_arguments_are_einval_without_a_device():
         assert lib.otho_tree_ordered_grid(0, order) == 0 and lib.otho_tree_ordered_grid(-1, order) == EINVAL
 
 
-def kernel_notes(tmp_path):
-    """name -> notes of every kernel of every code object of the library."""
-    fb = str(tmp_path / "fb.bin")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, _lib.LIB_PATH,
-                           str(tmp_path / "host.so")])
-    blob = open(fb, "rb").read()
-    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)] + [len(blob)]
-    found = {}
-    for i in range(len(starts) - 1):
-        part, co = str(tmp_path / f"fb{i}.bin"), str(tmp_path / f"co{i}.o")
-        open(part, "wb").write(blob[starts[i]:starts[i + 1]])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-        notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
-        for block in notes.split("- .agpr_count")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", block).group(1)
-            found[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
-                           for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count")}
-    return found
-
-
-def test_ordered_kernels_keep_the_unordered_kernels_lds_and_use_no_scratch(tmp_path):
+def test_ordered_kernels_keep_the_unordered_kernels_lds_and_use_no_scratch():
     """Only the current frame scores, in registers: the frames keep their 9
     words, so the LDS per block is the unordered kernels' (16,320 B for search
     and tree, 16,512 B for play), none of the searches' eight kernels has
     scratch, and eight one-wave blocks still share a CU."""
-    if not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("ROCm LLVM tools not present")
-    k = kernel_notes(tmp_path)
+    k = codeobj.kernels()
 
     def one(sub):
         hit = [n for n in k if sub in n]

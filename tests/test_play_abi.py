@@ -3,10 +3,10 @@
 search's resource budget: no scratch, eight one-wave blocks per CU, at most 128
 VGPRs (host only)."""
 import ctypes
-import os
 import re
 import subprocess
 
+import codeobj
 from subproc_amd import _lib
 
 
@@ -61,38 +61,16 @@ def test_header_constants_match_the_binding():
     assert "OTHM_SEARCHED" in src and "OTHM_INVALID" in src and "OTHM_LIMIT" in src and "OTH_MOVES_STRIDE" in src
 
 
-LLVM = "/opt/rocm/lib/llvm/bin"
-
-
-def test_play_kernel_is_scratch_free_and_fits_eight_blocks(tmp_path):
-    """As the search's: the play kernel's bundle is found by its name, once; no
-    scratch (the stack is LDS, the game's state registers), an LDS footprint
-    that lets eight one-wave blocks share a CU's 160 KB, and at most 128 VGPRs."""
-    import pytest
-
-    if not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("ROCm LLVM tools not present")
-    fb = str(tmp_path / "fb.bin")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, _lib.LIB_PATH,
-                           str(tmp_path / "host.so")])
-    blob = open(fb, "rb").read()
-    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)] + [len(blob)]
-    found = []
-    for i in range(len(starts) - 1):
-        part, co = str(tmp_path / f"fb{i}.bin"), str(tmp_path / f"co{i}.o")
-        open(part, "wb").write(blob[starts[i]:starts[i + 1]])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-        notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
-        for block in notes.split("- .agpr_count")[1:]:
-            # the mangled name's length prefix tells play_kernel from replay_kernel
-            if "11play_kernel" in block:
-                found.append({k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
-                              for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count")})
-                # and the names the earlier code-object tests look for do not find it
-                assert not any(s in block for s in ("search_kernel", "solve_kernel", "rollout_kernel"))
+def test_play_kernel_is_scratch_free_and_fits_eight_blocks():
+    """As the search's: the play kernel is found by its name, once; no scratch
+    (the stack is LDS, the game's state registers), an LDS footprint that lets
+    eight one-wave blocks share a CU's 160 KB, and at most 128 VGPRs."""
+    # the mangled name's length prefix tells play_kernel from replay_kernel
+    found = {name: v for name, v in codeobj.kernels().items() if "11play_kernel" in name}
     assert len(found) == 1, found
-    k = found[0]
+    # and the names the earlier code-object tests look for do not find it
+    assert not any(s in name for name in found for s in ("search_kernel", "solve_kernel", "rollout_kernel"))
+    k = next(iter(found.values()))
     print(k)
     assert k["private_segment_fixed_size"] == 0
     assert k["group_segment_fixed_size"] * 8 <= 160 * 1024

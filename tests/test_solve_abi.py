@@ -7,6 +7,7 @@ import subprocess
 
 import numpy as np
 
+import codeobj
 import oracle
 import solve_ref
 from subproc_amd import _lib
@@ -116,35 +117,11 @@ def test_checker_lowest_maximiser_and_turn_rule():
         assert (vo == vb).all() and (mo == mb).all()
 
 
-LLVM = "/opt/rocm/lib/llvm/bin"
-
-
-def test_solve_kernel_is_scratch_free_and_fits_eight_blocks(tmp_path):
-    """The library's .hip_fatbin holds one bundle per source file; the solver's
-    is found by its kernel name.  No scratch (the search stack is LDS), and an
+def test_solve_kernel_is_scratch_free_and_fits_eight_blocks():
+    """The solver's kernel is found by its name among the library's code
+    objects (tests/codeobj.py).  No scratch (the search stack is LDS), and an
     LDS footprint that lets eight one-wave blocks share a CU's 160 KB."""
-    import os
-
-    import pytest
-
-    if not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("ROCm LLVM tools not present")
-    fb = str(tmp_path / "fb.bin")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, _lib.LIB_PATH,
-                           str(tmp_path / "host.so")])
-    blob = open(fb, "rb").read()
-    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)] + [len(blob)]
-    found = []
-    for i in range(len(starts) - 1):
-        part, co = str(tmp_path / f"fb{i}.bin"), str(tmp_path / f"co{i}.o")
-        open(part, "wb").write(blob[starts[i]:starts[i + 1]])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-        notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
-        for block in notes.split("- .agpr_count")[1:]:
-            if "solve_kernel" in block:
-                found.append({k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
-                              for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count")})
+    found = [v for name, v in codeobj.kernels().items() if "solve_kernel" in name]
     assert len(found) == 1, found
     k = found[0]
     assert k["private_segment_fixed_size"] == 0

@@ -8,11 +8,9 @@ import os
 import re
 import subprocess
 
-import pytest
-
+import codeobj
 from subproc_amd import _lib
 
-LLVM = "/opt/rocm/lib/llvm/bin"
 OTHERS = ("oth", "oths", "othm", "othp", "otht", "otho")
 
 
@@ -112,39 +110,14 @@ def test_scratch_bytes_and_grid_edges_need_no_device():
     assert lib.othe_solve_grid(0) == 0 and lib.othe_solve_grid(-1) == _lib.OTH_EINVAL
 
 
-def kernel_notes(tmp_path, wanted):
-    fb = str(tmp_path / "fb.bin")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, _lib.LIB_PATH,
-                           str(tmp_path / "host.so")])
-    blob = open(fb, "rb").read()
-    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)] + [len(blob)]
-    found = {}
-    for i in range(len(starts) - 1):
-        part, co = str(tmp_path / f"fb{i}.bin"), str(tmp_path / f"co{i}.o")
-        open(part, "wb").write(blob[starts[i]:starts[i + 1]])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-        notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
-        for block in notes.split("- .agpr_count")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", block).group(1)
-            for want in wanted:
-                if re.search(r"\d+%sE" % want, name):  # the mangled name ends the identifier there
-                    found.setdefault(want, []).append(
-                        {k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
-                         for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count")})
-    return found
-
-
-def test_task_kernels_are_scratch_free_at_the_solvers_lds_and_occupancy(tmp_path):
+def test_task_kernels_are_scratch_free_at_the_solvers_lds_and_occupancy():
     """No scratch in any of the four kernels; the two task kernels take no more
     LDS than solve_kernel (11 frames of 7 words, 19.25 KB: eight one-wave
     blocks in a CU's 160 KB) and stay in its occupancy class (two waves per
     SIMD: at most 256 VGPRs; they are held to 128)."""
-    if not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("ROCm LLVM tools not present")
     wanted = ("solve_kernel", "split_solve_tasks", "split_solve_tasks_ordered", "split_solve_expand",
               "split_solve_prefix")
-    found = kernel_notes(tmp_path, wanted)
+    found = codeobj.grouped(wanted, r"\d+%sE")  # the mangled name ends the identifier there
     assert {k: len(v) for k, v in found.items()} == {k: 1 for k in wanted}, found
     for name, (k,) in found.items():
         assert k["private_segment_fixed_size"] == 0, name

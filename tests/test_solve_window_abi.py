@@ -10,10 +10,10 @@ import subprocess
 
 import pytest
 
+import codeobj
 from subproc_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LLVM = "/opt/rocm/lib/llvm/bin"
 OTHERS = ("oth", "oths", "othm", "othp", "otht", "otho", "othe", "othh")
 
 
@@ -132,35 +132,11 @@ def test_engine_checks_solve_wld_empties():
     assert engine.Engine().solve_wld_empties == 0
 
 
-def kernel_resources(tmp_path, wanted):
-    """name -> resources of the gfx950 kernels whose name holds one of `wanted`"""
-    fb = str(tmp_path / "fb.bin")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, _lib.LIB_PATH,
-                           str(tmp_path / "host.so")])
-    blob = open(fb, "rb").read()
-    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)] + [len(blob)]
-    found = {}
-    for i in range(len(starts) - 1):
-        part, co = str(tmp_path / f"fb{i}.bin"), str(tmp_path / f"co{i}.o")
-        open(part, "wb").write(blob[starts[i]:starts[i + 1]])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-        notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
-        for block in notes.split("- .agpr_count")[1:]:
-            name = re.search(r"\.name:\s+(\S+)", block).group(1)
-            if any(k in name for k in wanted):
-                found[name] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
-                               for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count")}
-    return found
-
-
-def test_the_windowed_kernels_keep_the_solvers_footprint(tmp_path):
+def test_the_windowed_kernels_keep_the_solvers_footprint():
     """One-wave blocks with the frames in LDS ([depth][field][lane], 19.25 KB),
     no scratch, and registers for two waves per SIMD: eight blocks share a CU,
     as before the window (DESIGN.md §20 has the figures beside the parent's)."""
-    if not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("ROCm LLVM tools not present")
-    found = kernel_resources(tmp_path, ("solve_windowed", "split_window_tasks"))
+    found = codeobj.named(("solve_windowed", "split_window_tasks"))
     # the one-lane kernel and the task kernel plain or hashed, in either move order
     assert len(found) == 5 and sum("solve_windowed" in k for k in found) == 1, sorted(found)
     for name, k in found.items():

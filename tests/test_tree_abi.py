@@ -3,13 +3,11 @@ beside the oth_*, oths_*, othm_* and othp_* sets, its constants match the
 binding, and its task kernel keeps the stack in LDS at the search's own
 occupancy (CPU only; resources, not instructions)."""
 import ctypes
-import os
 import re
 import subprocess
 
+import codeobj
 from subproc_amd import _lib
-
-LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def header_functions(path, prefix):
@@ -70,36 +68,10 @@ def test_scratch_bytes_needs_no_device():
     assert lib.otht_search_grid(0) == 0 and lib.otht_search_grid(-1) == _lib.OTH_EINVAL
 
 
-def kernel_notes(tmp_path, wanted):
-    fb = str(tmp_path / "fb.bin")
-    subprocess.check_call([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fb, _lib.LIB_PATH,
-                           str(tmp_path / "host.so")])
-    blob = open(fb, "rb").read()
-    starts = [m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", blob)] + [len(blob)]
-    found = {}
-    for i in range(len(starts) - 1):
-        part, co = str(tmp_path / f"fb{i}.bin"), str(tmp_path / f"co{i}.o")
-        open(part, "wb").write(blob[starts[i]:starts[i + 1]])
-        subprocess.check_call([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
-                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + co])
-        notes = subprocess.check_output([os.path.join(LLVM, "llvm-readelf"), "--notes", co], text=True)
-        for block in notes.split("- .agpr_count")[1:]:
-            for name in wanted:
-                if name in block:
-                    found.setdefault(name, []).append(
-                        {k: int(re.search(r"\.%s:\s+(\d+)" % k, block).group(1))
-                         for k in ("private_segment_fixed_size", "group_segment_fixed_size", "vgpr_count")})
-    return found
-
-
-def test_tree_kernels_are_scratch_free_and_the_task_kernel_fits_eight_blocks(tmp_path):
+def test_tree_kernels_are_scratch_free_and_the_task_kernel_fits_eight_blocks():
     """As the search's: no scratch in any of the three kernels, and a task
     kernel whose LDS lets eight one-wave blocks share a CU's 160 KB."""
-    import pytest
-
-    if not os.path.exists(os.path.join(LLVM, "llvm-readelf")):
-        pytest.skip("ROCm LLVM tools not present")
-    found = kernel_notes(tmp_path, ("task_kernel", "expand_kernel", "prefix_kernel"))
+    found = codeobj.grouped(("task_kernel", "expand_kernel", "prefix_kernel"))
     assert {k: len(v) for k, v in found.items()} == {"task_kernel": 1, "expand_kernel": 1, "prefix_kernel": 1}, found
     for name, (k,) in found.items():
         assert k["private_segment_fixed_size"] == 0, name
