@@ -19,6 +19,7 @@ SOLVE_HASH_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_sol
 SOLVE_WINDOW_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_solve_window.h")
 MOVES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_moves.h")
 BUDGET_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_budget.h")
+LINE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_line.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -64,6 +65,8 @@ SOLVE_ALPHA_MIN, SOLVE_BETA_MAX = -65, 65
 MOVES_NOT_A_MOVE, MOVES_UNKNOWN = -128, -127  # include/othello_moves.h: the exact calls' int8 rows
 MOVES_NOT_A_MOVE32, MOVES_UNKNOWN32 = -2**31, -2**31 + 1  # the search's int32 rows
 MOVES_SEARCH_SLOTS = 64
+LINE_STRIDE = 32             # include/othello_line.h
+LINE_BADDEPTH = 6
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -192,6 +195,16 @@ BUDGET_SIGNATURES = {
     "othb_play_grid": (_I, [_I64]),
 }
 
+# the principal variation, include/othello_line.h (its own prefix likewise): oths_solve's / otho_search_ordered's
+# arguments with line, length in front of value and end_boards, end_turn in front of work; the search's with
+# depth_per_position after depth
+LINE_SIGNATURES = {
+    "othl_solve_line": (_I, [_P, _P, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "othl_search_line": (_I, [_P, _P, _I, _P, _I, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "othl_solve_line_grid": (_I, [_I64]),
+    "othl_search_line_grid": (_I, [_I64, _I]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -225,7 +238,7 @@ def load():
     for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES, **PLAY_SIGNATURES,
                               **TREE_SIGNATURES, **ORDER_SIGNATURES, **SOLVE_TREE_SIGNATURES,
                               **SOLVE_HASH_SIGNATURES, **SOLVE_WINDOW_SIGNATURES, **MOVES_SIGNATURES,
-                              **BUDGET_SIGNATURES}.items():
+                              **BUDGET_SIGNATURES, **LINE_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -25,6 +25,14 @@ policy into GameRunner unchanged:
                    equals), or the one line "hint unavailable" (policies random
                    and greedy outside --solve-empties); then an empty line.
                    Nothing is played.  Player never sends it.
+  pv            -> one line "<value> <move> <move> ...": the line of best play
+                   from the side to move (PS for a pass) and its value, from
+                   ops.solve_line within --solve-empties (at most 12 empties),
+                   else from ops.search_line for policy search (at --depth, or
+                   the depth the last budget search reached) and policy eval
+                   (depth 1); or the one line "pv unavailable" (policies random
+                   and greedy, --split, more than 12 empties in the exact
+                   range).  Nothing is played.  Player never sends it.
 
 Rules and move generation run on the GPU through the drop-in Board
 (subproc_amd.board); the move choice is the env's policy: "random" (uniform
@@ -251,6 +259,35 @@ class Engine:
             return ["%s %d" % (handstr_from_coord(sq & 7, sq >> 3).upper(), row[sq]) for sq in best]
         return ["hint unavailable"]
 
+    def pv(self):
+        """The `pv` command's line: "<value> <move> <move> ..." (Edax move
+        strings, PS for a pass), the line of best play from the side to move
+        and the value it stands for, or "pv unavailable".  Within solve_empties
+        it is ops.solve_line's (at most 12 empties: there is no line through
+        the split solver; the final disc difference), whatever the policy; else
+        ops.search_line's for policy search at the engine's depth (with nodes:
+        the depth the last go reached) and for policy eval at depth 1 (the
+        eval's units).  Policies random and greedy have no line of their own,
+        and there is none through the split search."""
+        if self.board.turn not in (gboard.Black, gboard.White):
+            return "pv unavailable"
+        boards, side, empties = self._position()
+        r = None
+        if 0 < self.solve_empties and empties <= self.solve_empties:
+            if empties > _lib.SOLVE_MAX_EMPTIES:
+                return "pv unavailable"
+            r = ops.solve_line(boards, side, max_empties=min(self.solve_empties, _lib.SOLVE_MAX_EMPTIES),
+                               node_limit=1 << 24)
+        elif self.policy in ("search", "eval") and self.split == 0:
+            depth = 1 if self.policy == "eval" else self.depth if self.nodes is None else (self.reached or 0)
+            if 1 <= depth <= _lib.SEARCH_MAX_DEPTH:
+                r = ops.search_line(boards, side, depth, weights=self.weights, order=self.order, node_limit=1 << 24)
+        if r is None or int(r.status.cpu()[0]) != _lib.SOLVE_SOLVED:  # (== SEARCH_SEARCHED)
+            return "pv unavailable"
+        line = r.line[0, :int(r.length.cpu()[0])].cpu().tolist()
+        return " ".join(["%d" % int(r.value.cpu()[0])] + [
+            "PS" if sq == _lib.PASS else handstr_from_coord(sq & 7, sq >> 3).upper() for sq in line])
+
     def choose(self):
         b = self.board
         puts = b.puttables(b.turn)
@@ -287,6 +324,8 @@ class Engine:
             for t in self.hint():
                 out(t)
             out("")
+        elif cmd == "pv":
+            out(self.pv())
         elif cmd == "verbose p":
             extra = " weights=%s" % self.weights.reshape(-1).tolist() if self.policy in ("eval", "search") else ""
             if self.policy == "search":

@@ -116,6 +116,21 @@ class VecEnv:
         return ops.search_moves(self.boards, self.turn, depth, weights=weights, node_limit=node_limit,
                                 want_nodes=want_nodes)
 
+    def solve_line(self, max_empties=12, node_limit=0, want_nodes=False):
+        """The line of perfect play from the current state (ops.solve_line):
+        per game up to 32 move codes (64 = pass, 255 = padding) beside solve()'s
+        value and move, and the position where the line ends."""
+        return ops.solve_line(self.boards, self.turn, max_empties=max_empties, node_limit=node_limit,
+                              want_nodes=want_nodes)
+
+    def search_line(self, depth, weights=None, order=0, node_limit=0, want_nodes=False):
+        """The line of the `depth`-ply search from the current state
+        (ops.search_line), every leaf scored from the mover's side: per game the
+        moves down to the horizon beside search()'s value and move.  `depth` is
+        an int or one uint8 per game (search_budget's `depth` output fits)."""
+        return ops.search_line(self.boards, self.turn, depth, weights=weights, order=order, node_limit=node_limit,
+                               want_nodes=want_nodes)
+
     def books(self):
         """Book text (serialize_str, board.py:214-221) of every game: oth_book_text
         on the device, one 67-byte line per game, decoded on the host."""

@@ -878,6 +878,97 @@ def search_moves(boards, turn, depth, weights=None, node_limit=0, want_nodes=Fal
                        work)
 
 
+LineResult = namedtuple("LineResult", "line length value best_move status nodes end_boards end_turn")
+
+
+def _line_call(name, fn, head, boards, turn, n, dtype, want_nodes, work):
+    """The shared half of :func:`solve_line` and :func:`search_line`: the
+    outputs, the work word, and the call ``fn(boards, turn, *head, line,
+    length, value, best_move, status, nodes, end_boards, end_turn, work, n,
+    stream)``."""
+    d = boards.device
+    pb = _dev(boards, "boards", torch.int64)
+    pt = _dev(turn, "turn", torch.uint8, (n,), d)
+    line = torch.empty((n, _lib.LINE_STRIDE), dtype=torch.uint8, device=d)
+    length = torch.empty(n, dtype=torch.uint8, device=d)
+    val, mv, st, nd = _outputs(n, dtype, want_nodes, d)
+    end = torch.empty((n, 2), dtype=torch.int64, device=d)
+    end_turn = torch.empty(n, dtype=torch.uint8, device=d)
+    _launch(name, fn, (pb, pt, *head, line.data_ptr(), length.data_ptr(), val.data_ptr(), mv.data_ptr(),
+                       st.data_ptr(), _ptr(nd), end.data_ptr(), end_turn.data_ptr(), _work_ptr(work, d), n), work, d)
+    return LineResult(line, length, val, mv, st, nd, end, end_turn)
+
+
+def solve_line(boards, turn, max_empties=12, node_limit=0, want_nodes=False, work=None):
+    """The line of perfect play (othl_solve_line, include/othello_line.h):
+    :func:`solve`'s answer for each position with at most ``max_empties``
+    (0..12) empties, and behind it the sequence of best moves and replies the
+    value stands for, down to the end of the game.
+
+    Returns LineResult(line uint8 (n, 32), length uint8, value int8, best_move
+    uint8, status uint8, nodes, end_boards int64 (n, 2), end_turn uint8).
+    ``line[i, :length[i]]`` are move codes (0..63, 64 for a pass), the rest is
+    255; every entry is the lowest square among the best moves of the side to
+    move there, so ``line[i, 0]`` is ``best_move[i]`` and a finished game has an
+    empty line.  ``end_boards`` / ``end_turn`` are the position where the line
+    ends and the side to move there: its disc difference from the root mover's
+    side is ``value``.  ``value``, ``best_move`` and ``status`` are
+    :func:`solve`'s.  ``node_limit`` bounds each search of the walk (one per
+    entry of the line and one for the root); a position the root search
+    resolves under it is resolved whole, one it does not is SOLVE_LIMIT with an
+    empty line, 0 and 255.  ``nodes`` (with ``want_nodes``) sums the walk's
+    searches.
+
+    One launch; ``work`` as in :func:`solve`; the call may be captured in a
+    graph with an explicit work word.  No split solver and no root window here.
+    """
+    n = _n(boards)
+    _check32("node_limit", int(node_limit))
+    _dev(boards, "boards", torch.int64)  # (a host tensor is refused before anything asks the device)
+    _capturing("solve_line", work)
+    return _line_call("othl_solve_line", _lib.load().othl_solve_line, (int(max_empties), int(node_limit)), boards,
+                      turn, n, torch.int8, want_nodes, work)
+
+
+def search_line(boards, turn, depth, weights=None, order=0, node_limit=0, want_nodes=False, work=None):
+    """The line of the depth-limited search (othl_search_line,
+    include/othello_line.h): :func:`search`'s answer at ``depth`` and behind it
+    the sequence of best moves and replies down to the horizon (or the end of
+    the game), every leaf scored from the ROOT mover's side — what a host loop
+    of :func:`search` and :func:`step` cannot give, as it would score the second
+    ply's leaves from the other side.
+
+    ``depth`` is an int 1..8, or a uint8 (n,) device tensor with one depth per
+    position: an entry of 0 is not searched (empty line, value 0, move 255,
+    SEARCH_LIMIT — what :func:`search_budget` answers where not even depth 1
+    fitted, so its ``depth`` output can be passed straight in), an entry above 8
+    ends as _lib.LINE_BADDEPTH.
+
+    Returns LineResult as :func:`solve_line` with ``value`` int32.  The end
+    position's static score from the root mover's side is ``value``:
+    :func:`evaluate` of it at a leaf, 2**17 times the disc difference where the
+    game is over.  A line at a depth of at least the number of empties is
+    :func:`solve_line`'s.  ``order`` = 1 walks with the ordered search: the same
+    line from smaller trees, other ``nodes``.  ``node_limit`` as in
+    :func:`solve_line` (with ``order`` = 1 a position within reach of it may end
+    differently).  One launch; ``work`` as in :func:`search`; capturable with an
+    explicit work word.  No split search here.
+    """
+    n = _n(boards)
+    _check32("node_limit", int(node_limit))
+    _dev(boards, "boards", torch.int64)  # (a host tensor is refused before anything asks the device)
+    _capturing("search_line", work)
+    if isinstance(depth, torch.Tensor):
+        scalar, per = 0, _dev(depth, "depth", torch.uint8, (n,), boards.device)
+    else:
+        scalar, per = int(depth), None
+        if not 1 <= scalar <= _lib.SEARCH_MAX_DEPTH:
+            raise ValueError(f"depth must lie in 1..{_lib.SEARCH_MAX_DEPTH}")
+    return _line_call("othl_search_line", _lib.load().othl_search_line,
+                      (scalar, per, int(order), _weights_ptr(weights), int(node_limit)), boards, turn, n, torch.int32,
+                      want_nodes, work)
+
+
 PlayResult = namedtuple("PlayResult", "final_boards diff plies moves hist a_black status nodes")
 
 
@@ -1095,6 +1186,7 @@ def from_numpy_u64(a, device="cuda"):
 __all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", "solve", "SolveTable", "search", "play",
            "search_budget", "BudgetResult",
            "solve_moves", "search_moves", "MovesResult",
+           "solve_line", "search_line", "LineResult",
            "sample_midgame",
            "replay",
            "book_text", "features", "evaluate", "to_numpy_u64", "from_numpy_u64",
