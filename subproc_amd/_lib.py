@@ -20,6 +20,7 @@ SOLVE_WINDOW_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_s
 MOVES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_moves.h")
 BUDGET_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_budget.h")
 LINE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_line.h")
+PLAY_SOLVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_play_solve.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -67,6 +68,7 @@ MOVES_NOT_A_MOVE32, MOVES_UNKNOWN32 = -2**31, -2**31 + 1  # the search's int32 r
 MOVES_SEARCH_SLOTS = 64
 LINE_STRIDE = 32             # include/othello_line.h
 LINE_BADDEPTH = 6
+PLAY_SOLVE_COUNTER_BYTES, PLAY_SOLVE_PARKED_BYTES = 16, 48  # include/othello_play_solve.h
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -205,6 +207,15 @@ LINE_SIGNATURES = {
     "othl_search_line_grid": (_I, [_I64, _I]),
 }
 
+# search self-play with the exact solver's endgame, include/othello_play_solve.h (its own prefix likewise):
+# othb_play's arguments with solve_empties where exact_empties stands and scratch, scratch_bytes in front of work
+PLAY_SOLVE_SIGNATURES = {
+    "othx_play": (_I, [_P, _P, _U64, _U64, _P, _P, _I, _I, ctypes.c_uint32, ctypes.c_uint32, _I, _I, _I, _I, _I,
+                       ctypes.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _I64, _P]),
+    "othx_scratch_bytes": (_I64, [_I64]),
+    "othx_play_grid": (_I, [_I64, _I, _I]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -238,7 +249,7 @@ def load():
     for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES, **PLAY_SIGNATURES,
                               **TREE_SIGNATURES, **ORDER_SIGNATURES, **SOLVE_TREE_SIGNATURES,
                               **SOLVE_HASH_SIGNATURES, **SOLVE_WINDOW_SIGNATURES, **MOVES_SIGNATURES,
-                              **BUDGET_SIGNATURES, **LINE_SIGNATURES}.items():
+                              **BUDGET_SIGNATURES, **LINE_SIGNATURES, **PLAY_SOLVE_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

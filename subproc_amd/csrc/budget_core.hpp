@@ -114,7 +114,7 @@ struct Budgets {
 // One step of a live game's lane: play_core.hpp's advance() with the deepening
 // layer.  m.depth[] are the caps; m.limit bounds the searches without a budget
 // (those at empties <= m.exact_empties).  D.d == 0 at a game's begin.
-template <class R, bool kOrdered, class S, class Out>
+template <class R, bool kOrdered, bool kPark = false, class S, class Out>
 OTHM_FN void advance_play(othp::Game& G, othm::Lane& L, othm::Order& Q, Deepen& D, S& stk, const int* tables,
                           const othp::Match& m, const Budgets& b, Out& out) {
     if (L.depth >= 0) {
@@ -136,7 +136,7 @@ OTHM_FN void advance_play(othp::Game& G, othm::Lane& L, othm::Order& Q, Deepen& 
         }
     }
     if (L.depth < 0) {
-        othp::step<R>(G, L, m, out);
+        othp::step<R, kPark>(G, L, m, out);
         if constexpr (kOrdered) othm::order_reset(Q);
         if (L.depth >= 0 && 64 - R::count(G.P | G.O) > m.exact_empties) {
             // the search step() has just started becomes iteration 1 of the mover's budget

@@ -81,6 +81,7 @@ struct Match {
 
 constexpr u32 kMoveNone = 255;    // Game::next: nothing decided, analyse the position
 constexpr u32 kMoveSearch = 254;  // Game::next: the move is the running search's
+constexpr u32 kParked = 0;        // Game::status of a game step<R, true>() took out of play: no output carries it
 
 struct Game {
     u64 P, O;         // the mover's discs, the other side's
@@ -145,7 +146,10 @@ OTHM_FN void hand_over(Game& G) {
 // One step of a live game whose lane is not searching (L.depth < 0).  `out`
 // receives every move: out.move(ply, code).  The game has ended when G.live is
 // false on return; a search has started when L.depth >= 0.
-template <class R, class Out>
+// kPark (play_solve.hip's first phase): a game whose turn begins with at most
+// m.exact_empties empty squares is not played on: it leaves as kParked, no draw
+// of that turn made, for the exact endgame (play_solve_core.hpp) to take up.
+template <class R, bool kPark = false, class Out>
 OTHM_FN void step(Game& G, othm::Lane& L, const Match& m, Out& out) {
     u32 mv = G.next;
     if (mv == kMoveSearch) {
@@ -170,6 +174,13 @@ OTHM_FN void step(Game& G, othm::Lane& L, const Match& m, Out& out) {
         G.P = np;
         out.move(G.ply, mv);
         hand_over(G);
+    }
+    if constexpr (kPark) {
+        if (64 - R::count(G.P | G.O) <= m.exact_empties) {
+            G.status = kParked;
+            G.live = false;
+            return;
+        }
     }
     const u64 own = R::moves(G.P, G.O);
     if (own == 0) {
@@ -210,7 +221,7 @@ OTHM_FN void step(Game& G, othm::Lane& L, const Match& m, Out& out) {
 // (2 x othm::kEvalTable ints); each search reads its mover's.  kOrdered: both
 // players search with order_core.hpp's machine (the games' moves are the same);
 // Q is the lane's scoring state, reset with every new root, and unused otherwise.
-template <class R, bool kOrdered, class S, class Out>
+template <class R, bool kOrdered, bool kPark = false, class S, class Out>
 OTHM_FN void advance(Game& G, othm::Lane& L, othm::Order& Q, S& stk, const int* tables, const Match& m, Out& out) {
     if (L.depth >= 0) {
         if constexpr (kOrdered)
@@ -219,7 +230,7 @@ OTHM_FN void advance(Game& G, othm::Lane& L, othm::Order& Q, S& stk, const int* 
             othm::advance<R>(L, stk, tables + othm::kEvalTable * (int)mover_player(G), m.limit);
     }
     if (L.depth < 0) {
-        step<R>(G, L, m, out);
+        step<R, kPark>(G, L, m, out);
         if constexpr (kOrdered) othm::order_reset(Q);
     }
 }

@@ -974,7 +974,7 @@ PlayResult = namedtuple("PlayResult", "final_boards diff plies moves hist a_blac
 
 def play(n, seed, game_id0=0, weights_a=None, weights_b=None, depth_a=1, depth_b=None, exact_empties=0, n_rand_a=0,
          n_rand_b=0, swap_colours=False, start=None, start_turn=None, record_moves=False, node_limit=0,
-         want_nodes=False, hist=None, device="cuda", work=None, order=0, budget=None):
+         want_nodes=False, hist=None, device="cuda", work=None, order=0, budget=None, solve_empties=0):
     """n whole games between two searching players in one launch (othp_play,
     include/othello_play.h): :func:`rollout_runner`'s match schedule -- player
     A against player B, the colour draw, the random-move budgets -- with every
@@ -1004,7 +1004,22 @@ def play(n, seed, game_id0=0, weights_a=None, weights_b=None, depth_a=1, depth_b
     being the depth caps (othb_play, include/othello_budget.h); the searches
     from ``exact_empties`` on keep ``node_limit`` and take no budget; ``nodes``
     sums the completed iterations.  A game then costs at most its plies times
-    the budget, whatever its positions.  None: today's fixed-depth games."""
+    the budget, whatever its positions.  None: today's fixed-depth games.
+
+    ``solve_empties`` = E in 1..12: once a position has at most E empty squares
+    the policy move is :func:`solve`'s best move, from the exact solver's own
+    machine (othx_play, include/othello_play_solve.h: the games leave the
+    search's kernel for the solver's where they reach E empties).  Up to 8 the
+    games are those of ``exact_empties`` = E; above it they are the ones the
+    engine's ``--solve-empties`` plays.  ``node_limit`` bounds every solve too,
+    ``nodes`` sums searches and solves, and a launch lasts as long as its
+    hardest game's solves.  It takes the place of ``exact_empties`` (only one of
+    the two may be non-zero); 0: the calls above, unchanged."""
+    solve_empties = int(solve_empties)
+    if not 0 <= solve_empties <= _lib.SOLVE_MAX_EMPTIES:
+        raise ValueError("solve_empties must lie in 0..%d" % _lib.SOLVE_MAX_EMPTIES)
+    if solve_empties and int(exact_empties):
+        raise ValueError("solve_empties takes the place of exact_empties: only one of the two may be non-zero")
     budgets = ()
     if budget is not None:
         budgets = (int(budget),) * 2 if isinstance(budget, numbers.Integral) else tuple(int(b) for b in budget)
@@ -1035,11 +1050,21 @@ def play(n, seed, game_id0=0, weights_a=None, weights_b=None, depth_a=1, depth_b
         lib.othp_play, "othp_play", ())
     if budgets:
         fn, name, ordered = lib.othb_play, "othb_play", (int(order),)
+    zone, scratch = int(exact_empties), ()
+    if solve_empties:
+        fn, name, ordered, zone = lib.othx_play, "othx_play", (int(order),), solve_empties
+        budgets = budgets or (0, 0)
+        size = lib.othx_scratch_bytes(n)
+        if size < 0:
+            check(int(size), "othx_scratch_bytes")
+        buf = torch.empty(int(size) // 8, dtype=torch.int64, device=d)
+        scratch = (buf.data_ptr(), buf.numel() * 8)
     _launch(name, fn, (ps, pst, seed & (2**64 - 1), game_id0, _weights_ptr(weights_a), _weights_ptr(weights_b),
-                       int(depth_a), int(depth_a if depth_b is None else depth_b), *budgets, int(exact_empties),
+                       int(depth_a), int(depth_a if depth_b is None else depth_b), *budgets, zone,
                        *ordered, int(n_rand_a), int(n_rand_b), int(bool(swap_colours)), int(node_limit), ab.data_ptr(),
-                       fb.data_ptr(), df.data_ptr(), pl.data_ptr(), _ptr(mv), st.data_ptr(), _ptr(nd), ph, pw, n),
-            work, d)
+                       fb.data_ptr(), df.data_ptr(), pl.data_ptr(), _ptr(mv), st.data_ptr(), _ptr(nd), ph, *scratch,
+                       pw, n), work, d)
+    # (the caching allocator hands the scratch to later work of THIS stream only)
     return PlayResult(fb, df, pl, mv, hist, ab, st, nd)
 
 

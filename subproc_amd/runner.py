@@ -52,7 +52,7 @@ def hamlet_param_line(name, policy, weights, depth=None, solve_empties=0, nodes=
 
 def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, policy="eval", name_a="Hamlet",
                name_b="GPU", device="cuda", record=True, win_rule="reference", store=None, depth=None,
-               exact_empties=0, order=0, budget=None):
+               exact_empties=0, order=0, budget=None, solve_empties=0):
     """n GameRunner games between A (``weights_a``) and B (``weights_b``,
     default params.DEFAULT_WEIGHTS), both playing ``policy``: "greedy", "eval",
     or "search" -- every policy move searched ``depth`` plies deep (an int, or
@@ -62,6 +62,9 @@ def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, po
     game that a search's node limit stopped (ops.play's status) raises.
     ``budget`` = B or (A's, B's): the moves are searched by node budget, ``depth``
     being the cap (ops.play(budget=...)); None: fixed depth.
+    ``solve_empties`` = E (1..12) in place of ``exact_empties``: from E empty
+    squares on the moves are the exact solver's (ops.play(solve_empties=...)),
+    as the engine's --solve-empties plays them; the parameter line names it.
 
     Game i is global id ``game_id0 + i`` (its book id).  ``record=True``
     replays every game into books (the recorder's view); the batch stats are
@@ -81,14 +84,15 @@ def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, po
         budget_a, budget_b = (budget, budget) if budget is None or isinstance(budget, int) else budget
         r = ops.play(n, seed, game_id0, wa, wb, depth_a, depth_b, exact_empties, n_rand_a, n_rand_b, swap,
                      record_moves=record, device=device, order=order,
-                     budget=None if budget is None else (budget_a, budget_b))
+                     budget=None if budget is None else (budget_a, budget_b), solve_empties=solve_empties)
         if not bool((r.status == ops._lib.SEARCH_SEARCHED).all()):
             raise RuntimeError("do_matches: a game's search reached the node limit")
-        line = {"a": hamlet_param_line(name_a, policy, wa, depth_a, exact_empties, budget_a),
-                "b": hamlet_param_line(name_b, policy, wb, depth_b, exact_empties, budget_b)}
+        zone = solve_empties or exact_empties  # (ops.play has refused both)
+        line = {"a": hamlet_param_line(name_a, policy, wa, depth_a, zone, budget_a),
+                "b": hamlet_param_line(name_b, policy, wb, depth_b, zone, budget_b)}
     else:
-        if depth is not None or exact_empties or budget is not None:
-            raise ValueError("depth, exact_empties and budget apply to policy 'search' only")
+        if depth is not None or exact_empties or budget is not None or solve_empties:
+            raise ValueError("depth, exact_empties, solve_empties and budget apply to policy 'search' only")
         if order:
             raise ValueError("order applies to policy 'search' only")
         r = ops.rollout_runner(n, seed, game_id0, policy, wa, wb, n_rand_a, n_rand_b, swap, record_moves=record,
