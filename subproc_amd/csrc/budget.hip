@@ -13,9 +13,8 @@
 // give the search and the games, in the same shape:
 //   * the rules, the LDS stack [depth][field][lane], the widened eval table(s)
 //     in LDS, one-wave blocks and a persistent loop;
-//   * the refill through the caller's work word at kRefillMin idle lanes, each
-//     lane making one failing request, the completing add resetting the word
-//     (0 at launch, left at 0);
+//   * the refill through the caller's work word at kRefillMin idle lanes
+//     (device_common.hpp's take());
 //   * per lane, in registers: the root's boards (the search kernel; a game has
 //     them already) and budget_core.hpp's Deepen (7 words).
 //
@@ -33,7 +32,7 @@
 #include "../../include/othello_search.h"
 #include "device_common.hpp"
 #include "budget_core.hpp"
-#include "game_out.hpp"
+#include "game_loop.hpp"
 
 static_assert(OTHM_MAX_DEPTH == othm::kMaxDepth && OTHM_SEARCHED == othm::kSearched &&
                   OTHM_INVALID == othm::kInvalid && OTHM_LIMIT == othm::kLimit && OTHM_NO_MOVE == othm::kNoMove &&
@@ -106,14 +105,8 @@ __device__ __forceinline__ void budget_search_body(const BudgetSearchArgs& a) {
         if ((wantm | busym) == 0) break;
         const u64 cnt = (u64)__popcll(wantm);
         if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
-            u64 base = 0;
-            if (lane == 0) {
-                base = atomicAdd(a.work, cnt);
-                if (base + cnt == a.total) atomicExch(a.work, 0ull);  // every request is made: reset
-            }
-            base = __shfl(base, 0);
+            const u64 g = othd::take(a.work, a.total, wantm, cnt, lane);
             if (want) {
-                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
                 if (g >= a.n) {
                     exhausted = true;
                 } else {
@@ -165,80 +158,13 @@ struct BudgetPlayArgs {
     int8_t w[2][OTH_EVAL_WEIGHTS];  // A's table, B's table
 };
 
-// the game's move record and othp_play's outputs: game_out.hpp
-using othp::emit;
-using othp::MoveRecord;
-
-// the persistent loop of both game kernels; kOrdered: order_core.hpp's machine
-template <bool kOrdered>
-__device__ __forceinline__ void budget_play_body(const BudgetPlayArgs& a) {
-    __shared__ u32 frames[othm::kFrames * othm::kFields * kBudgetBlock];
-    __shared__ int tables[2 * othm::kEvalTable];
-    const u32 lane = threadIdx.x;
-    if (lane < (u32)othm::kEvalTable) {
-        othm::widen_weight(a.w[0], (int)lane, tables);
-        othm::widen_weight(a.w[1], (int)lane, tables + othm::kEvalTable);
-    }
-    __syncthreads();
-    LdsStack stk{frames + lane};
-    othm::Lane L;
-    L.depth = -1;
-    othm::Order Q;  // (unused, and gone, when !kOrdered)
-    othm::order_reset(Q);
-    othb::Deepen D;
-    D.d = 0;
-    othp::Game G;
-    G.live = false;
-    MoveRecord rec{nullptr};
-    u64 idx = 0;
-    bool exhausted = false;  // the lane has made its failing request
-    for (;;) {
-        const bool idle = !G.live;
-        const bool want = idle && !exhausted;
-        const u64 wantm = __ballot(want);
-        const u64 busym = __ballot(!idle);
-        if ((wantm | busym) == 0) break;
-        const u64 cnt = (u64)__popcll(wantm);
-        if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
-            u64 base = 0;
-            if (lane == 0) {
-                base = atomicAdd(a.work, cnt);
-                if (base + cnt == a.total) atomicExch(a.work, 0ull);  // every request is made: reset
-            }
-            base = __shfl(base, 0);
-            if (want) {
-                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
-                if (g >= a.n) {
-                    exhausted = true;
-                } else {
-                    u64 black = othp::kOpenBlack, white = othp::kOpenWhite;
-                    bool white_to_move = false;
-                    if (a.start) {
-                        const ulonglong2 b = reinterpret_cast<const ulonglong2*>(a.start)[g];
-                        black = b.x;
-                        white = b.y;
-                        white_to_move = a.start_turn && a.start_turn[g] == OTH_WHITE;
-                    }
-                    rec.row = a.moves ? a.moves + g * OTH_MOVES_STRIDE : nullptr;
-                    rec.pad();
-                    othp::begin(G, L, a.match, othp::game_key(a.seed_state, a.game_id0 + g), black, white,
-                                white_to_move);
-                    D.d = 0;
-                    idx = g;
-                    if (!G.live) emit(a, g, G);  // overlapping boards
-                }
-            }
-        }
-        if (G.live) {
-            othb::advance_play<DeviceRules, kOrdered>(G, L, Q, D, stk, tables, a.match, a.budgets, rec);
-            if (!G.live) emit(a, idx, G);
-        }
-    }
+// the persistent loop of both game kernels is game_loop.hpp's, by budget and
+// without a parking step
+__global__ __launch_bounds__(kBudgetBlock) void budget_play_kernel(BudgetPlayArgs a) {
+    othp::game_body<kBudgetBlock, false, true>(a);
 }
-
-__global__ __launch_bounds__(kBudgetBlock) void budget_play_kernel(BudgetPlayArgs a) { budget_play_body<false>(a); }
 __global__ __launch_bounds__(kBudgetBlock) void budget_play_ordered_kernel(BudgetPlayArgs a) {
-    budget_play_body<true>(a);
+    othp::game_body<kBudgetBlock, true, true>(a);
 }
 
 // one cache per kernel: [0] the searches, [1] the games; order 0, then 1
@@ -295,43 +221,18 @@ int othb_play(const uint64_t* start, const uint8_t* start_turn, uint64_t seed, u
               uint32_t node_limit, uint8_t* a_black, uint64_t* final_boards, int8_t* diff, uint8_t* plies,
               uint8_t* moves, uint8_t* status, uint64_t* nodes, int64_t* hist, uint64_t* work, int64_t n,
               void* stream) {
-    if (order < 0 || order > OTHO_MAX_ORDER) return OTH_EINVAL;
-    if (n < 0 || !work || !weights_a || !weights_b || depth_a < 1 || depth_a > OTHM_MAX_DEPTH || depth_b < 1 ||
-        depth_b > OTHM_MAX_DEPTH || budget_a == 0 || budget_b == 0 || exact_empties < 0 ||
-        exact_empties > OTHM_MAX_DEPTH || n_rand_a < 0 || n_rand_b < 0)
+    if (!othp::game_args_ok(order, n, work, weights_a, weights_b, depth_a, depth_b, n_rand_a, n_rand_b) ||
+        budget_a == 0 || budget_b == 0 || exact_empties < 0 || exact_empties > OTHM_MAX_DEPTH)
         return OTH_EINVAL;
     if (n == 0) return OTH_OK;
     const int grid = grid_of(n, 1, order);
     if (grid <= 0) return status_of(hipErrorInvalidDevice);
     BudgetPlayArgs a;
-    a.start = start;
-    a.start_turn = start_turn;
-    a.a_black = a_black;
-    a.final_boards = final_boards;
-    a.diff = diff;
-    a.plies = plies;
-    a.moves = moves;
-    a.status = status;
-    a.nodes = nodes;
-    a.hist = reinterpret_cast<unsigned long long*>(hist);
-    a.work = reinterpret_cast<unsigned long long*>(work);
-    a.n = (u64)n;
-    a.total = (u64)n + (u64)grid * kBudgetBlock;
-    a.seed_state = othp::seed_state(seed);
-    a.game_id0 = game_id0;
-    a.match.depth[0] = depth_a;
-    a.match.depth[1] = depth_b;
-    a.match.n_rand[0] = (u32)std::min(n_rand_a, OTHP_MAX_RANDOM);
-    a.match.n_rand[1] = (u32)std::min(n_rand_b, OTHP_MAX_RANDOM);
-    a.match.exact_empties = exact_empties;
-    a.match.limit = node_limit ? node_limit : OTHM_DEFAULT_NODE_LIMIT;
-    a.match.swap = swap_colours != 0;
+    othp::fill_game(a, start, start_turn, seed, game_id0, weights_a, weights_b, depth_a, depth_b, exact_empties,
+                    n_rand_a, n_rand_b, swap_colours, node_limit, a_black, final_boards, diff, plies, moves, status,
+                    nodes, hist, work, n, (int64_t)grid * kBudgetBlock);
     a.budgets.budget[0] = budget_a;
     a.budgets.budget[1] = budget_b;
-    for (int k = 0; k < OTH_EVAL_WEIGHTS; k++) {
-        a.w[0][k] = weights_a[k];
-        a.w[1][k] = weights_b[k];
-    }
     if (order)
         budget_play_ordered_kernel<<<(unsigned)grid, kBudgetBlock, 0, (hipStream_t)stream>>>(a);
     else

@@ -8,8 +8,10 @@
 //     [depth][field][lane] in 32-bit words, so a wave's access is one word per
 //     bank whatever depth each lane is at.  9 words: search_core.hpp's frame,
 //     7: solve_core.hpp's;
-//   * kRefillMin, status_of(), env_int(), ResidentBlocks, and the grid sizing
-//     of every launch: launch_grid(), grid_answer().
+//   * kRefillMin and take(): the device side of the work word, a wave's refill
+//     of its idle lanes;
+//   * status_of(), env_int(), ResidentBlocks, and the grid sizing of every
+//     launch: launch_grid(), grid_answer().
 // Everything device-side is force-inlined: no kernel gets a symbol from here.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -30,6 +32,31 @@ typedef uint32_t u32;
 // idle lanes that make a wave refill from the work word.  Measured with the
 // solver (solve.hip's header); the other kernels take it over.
 constexpr int kRefillMin = 8;
+
+// THE WORK WORD, device side.  Every persistent kernel's items are handed out
+// by one 64-bit word of the caller's:
+//   * the word is 0 at launch;
+//   * a wave whose idle lanes (`wantm`, `cnt` of them) refill makes one atomic
+//     add of cnt by lane 0 and gives its wanting lanes base, base + 1, ... in
+//     lane order; a lane whose index is not below the launch's items has made
+//     its failing request and asks no more;
+//   * every lane of the grid makes exactly one failing request, so the
+//     launch's requests add up to `total` = items + lanes of the grid, and the
+//     add that completes the sum resets the word: it is 0 again when the
+//     launch ends, whatever the order the waves arrived in.
+// take() is that turn, straight-line: the ballots, the refill predicate and the
+// loop's break stay with the caller (moved in here they change the kernels'
+// code).  Every lane of the wave calls it; the value is the
+// lane's index where the lane is in wantm, and nothing elsewhere.
+__device__ __forceinline__ u64 take(unsigned long long* work, u64 total, u64 wantm, u64 cnt, u32 lane) {
+    u64 base = 0;
+    if (lane == 0) {
+        base = atomicAdd(work, cnt);
+        if (base + cnt == total) atomicExch(work, 0ull);  // every request is made: reset
+    }
+    base = __shfl(base, 0);
+    return base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
+}
 
 struct DeviceRules {
     static __device__ __forceinline__ u64 moves(u64 P, u64 O) { return oth::moves(P, O); }

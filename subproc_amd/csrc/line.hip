@@ -14,9 +14,8 @@
 // same shape:
 //   * the rules, the LDS stack [depth][field][lane], the widened eval table in
 //     LDS, one-wave blocks and a persistent loop;
-//   * the refill through the caller's work word at kRefillMin idle lanes, each
-//     lane making one failing request, the completing add resetting the word
-//     (0 at launch, left at 0);
+//   * the refill through the caller's work word at kRefillMin idle lanes
+//     (device_common.hpp's take());
 //   * per lane, in registers: line_core.hpp's Walk (the position the walk
 //     stands at, the root's answer, the nodes' sum) and the root's colour.
 // The line's bytes go straight to global memory as each move is settled: the
@@ -133,14 +132,8 @@ __global__ __launch_bounds__(kLineBlock) void line_exact_walk(LineArgs<int8_t> a
         if ((wantm | busym) == 0) break;
         const u64 cnt = (u64)__popcll(wantm);
         if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
-            u64 base = 0;
-            if (lane == 0) {
-                base = atomicAdd(a.work, cnt);
-                if (base + cnt == a.total) atomicExch(a.work, 0ull);  // every request is made: reset
-            }
-            base = __shfl(base, 0);
+            const u64 g = othd::take(a.work, a.total, wantm, cnt, lane);
             if (want) {
-                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
                 if (g >= a.n) {
                     exhausted = true;
                 } else {
@@ -192,14 +185,8 @@ __device__ __forceinline__ void line_depth_body(const LineArgs<int32_t>& a) {
         if ((wantm | busym) == 0) break;
         const u64 cnt = (u64)__popcll(wantm);
         if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
-            u64 base = 0;
-            if (lane == 0) {
-                base = atomicAdd(a.work, cnt);
-                if (base + cnt == a.total) atomicExch(a.work, 0ull);  // every request is made: reset
-            }
-            base = __shfl(base, 0);
+            const u64 g = othd::take(a.work, a.total, wantm, cnt, lane);
             if (want) {
-                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
                 if (g >= a.n) {
                     exhausted = true;
                 } else {

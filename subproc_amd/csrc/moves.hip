@@ -262,14 +262,8 @@ __global__ __launch_bounds__(kSearchBlock) void search_moves_kernel(SearchMovesA
         if ((wantm | busym) == 0) break;
         const u64 cnt = (u64)__popcll(wantm);
         if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
-            u64 base = 0;
-            if (lane == 0) {
-                base = atomicAdd(a.work, cnt);
-                if (base + cnt == total) atomicExch(a.work, 0ull);  // every request is made: reset
-            }
-            base = __shfl(base, 0);
+            const u64 g = othd::take(a.work, total, wantm, cnt, lane);
             if (want) {
-                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
                 if (g >= n) {
                     exhausted = true;
                 } else {

@@ -13,9 +13,8 @@
 //     into LDS (2 x 48 ints) by the block's one wave; a lane's search reads the
 //     table of its mover;
 //   * the refill: idle lanes take the next GAMES from the caller's work word,
-//     kRefillMin of them at a time by one atomic of lane 0, each lane making
-//     one failing request, the completing add resetting the word: search.hip's
-//     protocol at game granularity.
+//     kRefillMin of them at a time: device_common.hpp's take() at game
+//     granularity.
 // The game's state (boards, ply, LCG state and increment, the two budgets, the
 // colour bits, the game index, the node sum) stays in registers.  Move bytes
 // and the per-game outputs are plain vector stores; the histogram is three
@@ -23,7 +22,8 @@
 //
 // play_ordered_kernel is the same loop with order_core.hpp's ordered search
 // inside (include/othello_order.h, order = 1; play_core.hpp's advance() with
-// its flag set); both kernels are instances of play_body<>.
+// its flag set); both kernels are instances of game_loop.hpp's game_body<>,
+// which budget.hip's and play_solve.hip's game kernels are too.
 //
 // Bounds: a lane's loop ends.  Every search is bounded by node_limit (at most
 // that many steps that count a node, a constant number of others per node);
@@ -37,7 +37,7 @@
 #include "../../include/othello_search.h"
 #include "../../include/othello_order.h"
 #include "device_common.hpp"
-#include "game_out.hpp"
+#include "game_loop.hpp"
 #include "play_core.hpp"
 
 static_assert(OTHM_MAX_DEPTH == othm::kMaxDepth && OTHM_SEARCHED == othm::kSearched &&
@@ -54,11 +54,8 @@ using othm::u32;
 using othm::u64;
 
 constexpr int kPlayBlock = 64;  // one wave
-using othd::DeviceRules;
-using othd::kRefillMin;
 using othd::status_of;
-using LdsStack = othd::LdsStack9<kPlayBlock>;
-static_assert(LdsStack::kFields == othm::kFields, "the frame's words");
+static_assert(othd::LdsStack9<kPlayBlock>::kFields == othm::kFields, "the frame's words");
 
 struct PlayArgs {
     const u64* start;
@@ -80,76 +77,14 @@ struct PlayArgs {
     int8_t w[2][OTH_EVAL_WEIGHTS];  // A's table, B's table
 };
 
-// the game's move record and its outputs: game_out.hpp
-using othp::emit;
-using othp::MoveRecord;
-
-// the persistent loop of both kernels; kOrdered: order_core.hpp's machine
-template <bool kOrdered>
-__device__ __forceinline__ void play_body(const PlayArgs& a) {
-    __shared__ u32 frames[othm::kFrames * othm::kFields * kPlayBlock];
-    __shared__ int tables[2 * othm::kEvalTable];
-    const u32 lane = threadIdx.x;
-    if (lane < (u32)othm::kEvalTable) {
-        othm::widen_weight(a.w[0], (int)lane, tables);
-        othm::widen_weight(a.w[1], (int)lane, tables + othm::kEvalTable);
-    }
-    __syncthreads();
-    LdsStack stk{frames + lane};
-    othm::Lane L;
-    L.depth = -1;
-    othm::Order Q;  // (unused, and gone, when !kOrdered)
-    othm::order_reset(Q);
-    othp::Game G;
-    G.live = false;
-    MoveRecord rec{nullptr};
-    u64 idx = 0;
-    bool exhausted = false;  // the lane has made its failing request
-    for (;;) {
-        const bool idle = !G.live;
-        const bool want = idle && !exhausted;
-        const u64 wantm = __ballot(want);
-        const u64 busym = __ballot(!idle);
-        if ((wantm | busym) == 0) break;
-        const u64 cnt = (u64)__popcll(wantm);
-        if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
-            u64 base = 0;
-            if (lane == 0) {
-                base = atomicAdd(a.work, cnt);
-                if (base + cnt == a.total) atomicExch(a.work, 0ull);  // every request is made: reset
-            }
-            base = __shfl(base, 0);
-            if (want) {
-                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
-                if (g >= a.n) {
-                    exhausted = true;
-                } else {
-                    u64 black = othp::kOpenBlack, white = othp::kOpenWhite;
-                    bool white_to_move = false;
-                    if (a.start) {
-                        const ulonglong2 b = reinterpret_cast<const ulonglong2*>(a.start)[g];
-                        black = b.x;
-                        white = b.y;
-                        white_to_move = a.start_turn && a.start_turn[g] == OTH_WHITE;
-                    }
-                    rec.row = a.moves ? a.moves + g * OTH_MOVES_STRIDE : nullptr;
-                    rec.pad();
-                    othp::begin(G, L, a.match, othp::game_key(a.seed_state, a.game_id0 + g), black, white,
-                                white_to_move);
-                    idx = g;
-                    if (!G.live) emit(a, g, G);  // overlapping boards
-                }
-            }
-        }
-        if (G.live) {
-            othp::advance<DeviceRules, kOrdered>(G, L, Q, stk, tables, a.match, rec);
-            if (!G.live) emit(a, idx, G);
-        }
-    }
+// the persistent loop of both kernels is game_loop.hpp's, by fixed depth and
+// without a parking step
+__global__ __launch_bounds__(kPlayBlock) void play_kernel(PlayArgs a) {
+    othp::game_body<kPlayBlock, false, false>(a);
 }
-
-__global__ __launch_bounds__(kPlayBlock) void play_kernel(PlayArgs a) { play_body<false>(a); }
-__global__ __launch_bounds__(kPlayBlock) void play_ordered_kernel(PlayArgs a) { play_body<true>(a); }
+__global__ __launch_bounds__(kPlayBlock) void play_ordered_kernel(PlayArgs a) {
+    othp::game_body<kPlayBlock, true, false>(a);
+}
 
 // one cache for play_kernel (order 0), one for the ordered kernel (1)
 othd::ResidentBlocks g_resident[2];
@@ -169,40 +104,16 @@ int otho_play_ordered(const uint64_t* start, const uint8_t* start_turn, uint64_t
                       int order, int n_rand_a, int n_rand_b, int swap_colours, uint32_t node_limit, uint8_t* a_black,
                       uint64_t* final_boards, int8_t* diff, uint8_t* plies, uint8_t* moves, uint8_t* status,
                       uint64_t* nodes, int64_t* hist, uint64_t* work, int64_t n, void* stream) {
-    if (order < 0 || order > OTHO_MAX_ORDER) return OTH_EINVAL;
-    if (n < 0 || !work || !weights_a || !weights_b || depth_a < 1 || depth_a > OTHM_MAX_DEPTH || depth_b < 1 ||
-        depth_b > OTHM_MAX_DEPTH || exact_empties < 0 || exact_empties > OTHM_MAX_DEPTH || n_rand_a < 0 || n_rand_b < 0)
+    if (!othp::game_args_ok(order, n, work, weights_a, weights_b, depth_a, depth_b, n_rand_a, n_rand_b) ||
+        exact_empties < 0 || exact_empties > OTHM_MAX_DEPTH)
         return OTH_EINVAL;
     if (n == 0) return OTH_OK;
     const int grid = play_grid(n, order);
     if (grid <= 0) return status_of(hipErrorInvalidDevice);
     PlayArgs a;
-    a.start = start;
-    a.start_turn = start_turn;
-    a.a_black = a_black;
-    a.final_boards = final_boards;
-    a.diff = diff;
-    a.plies = plies;
-    a.moves = moves;
-    a.status = status;
-    a.nodes = nodes;
-    a.hist = reinterpret_cast<unsigned long long*>(hist);
-    a.work = reinterpret_cast<unsigned long long*>(work);
-    a.n = (u64)n;
-    a.total = (u64)n + (u64)grid * kPlayBlock;
-    a.seed_state = othp::seed_state(seed);
-    a.game_id0 = game_id0;
-    a.match.depth[0] = depth_a;
-    a.match.depth[1] = depth_b;
-    a.match.n_rand[0] = (u32)std::min(n_rand_a, OTHP_MAX_RANDOM);
-    a.match.n_rand[1] = (u32)std::min(n_rand_b, OTHP_MAX_RANDOM);
-    a.match.exact_empties = exact_empties;
-    a.match.limit = node_limit ? node_limit : OTHM_DEFAULT_NODE_LIMIT;
-    a.match.swap = swap_colours != 0;
-    for (int k = 0; k < OTH_EVAL_WEIGHTS; k++) {
-        a.w[0][k] = weights_a[k];
-        a.w[1][k] = weights_b[k];
-    }
+    othp::fill_game(a, start, start_turn, seed, game_id0, weights_a, weights_b, depth_a, depth_b, exact_empties,
+                    n_rand_a, n_rand_b, swap_colours, node_limit, a_black, final_boards, diff, plies, moves, status,
+                    nodes, hist, work, n, (int64_t)grid * kPlayBlock);
     if (order)
         play_ordered_kernel<<<(unsigned)grid, kPlayBlock, 0, (hipStream_t)stream>>>(a);
     else

@@ -5,19 +5,19 @@
 // and in the solver's would execute both per step and hold both stacks (15.9 KB
 // of search frames and 19.25 KB of solver frames per one-wave block), so a game
 // changes kernels where it changes machines:
-//   * park_*_games: play.hip's and budget.hip's persistent loops, the same text
-//     around play_core.hpp's advance() / budget_core.hpp's advance_play() with
-//     their kPark flag set.  A game whose turn begins inside the zone (at most
+//   * park_*_games: play.hip's and budget.hip's persistent loop, game_loop.hpp's
+//     game_body<>, around play_core.hpp's advance() / budget_core.hpp's
+//     advance_play() with their kPark flag set.  A game whose turn begins inside the zone (at most
 //     solve_empties empty squares; its start included) comes back as
 //     othp::kParked: its record (play_solve_core.hpp's pack(): 48 B, three
 //     16-byte stores) goes to the slot one atomic on the list's counter names.
 //     Games that end above the zone are emitted as they always were.
 //   * finish_parked_games: line.hip's solver loop (one-wave blocks, the
 //     solver's frames in LDS indexed [depth][field][lane]) over the list.  The
-//     count is read on the device; the launch's requests add up to the count
-//     plus the grid's lanes, so the work word is back at 0 when the last one is
-//     made.  A lane plays its game to the end with play_solve_core.hpp's
-//     advance(); moves go to the game's row, the outputs are game_out.hpp's.
+//     count is read on the device, and with it the total that
+//     device_common.hpp's take() resets the work word at.  A lane plays its
+//     game to the end with play_solve_core.hpp's advance(); moves go to the
+//     game's row, the outputs are game_loop.hpp's.
 // The counter is zeroed by a memset node in front of the first launch; the two
 // launches are ordered by the stream, which makes the first one's stores
 // visible to the second.  The slots are handed out in whatever order the lanes
@@ -40,7 +40,7 @@
 #include "../../include/othello_solve.h"
 #include "device_common.hpp"
 #include "budget_core.hpp"
-#include "game_out.hpp"
+#include "game_loop.hpp"
 #include "play_solve_core.hpp"
 
 static_assert(OTHS_MAX_EMPTIES == oths::kMaxEmpties && OTHM_MAX_DEPTH == othm::kMaxDepth &&
@@ -66,11 +66,11 @@ constexpr int kBlock = 64;  // one wave
 using othd::DeviceRules;
 using othd::kRefillMin;
 using othd::status_of;
-using SearchStack = othd::LdsStack9<kBlock>;
 using SolveStack = othd::LdsStack7<kBlock>;
-static_assert(SearchStack::kFields == othm::kFields && SolveStack::kFields == oths::kFields, "the frames' words");
+static_assert(othd::LdsStack9<kBlock>::kFields == othm::kFields && SolveStack::kFields == oths::kFields,
+              "the frames' words");
 
-// both phases' arguments: othp_play's outputs by game_out.hpp's names, and the
+// both phases' arguments: othp_play's outputs by game_loop.hpp's names, and the
 // parked list (its counter, then its records)
 struct ZoneArgs {
     const u64* start;
@@ -99,97 +99,33 @@ using othp::emit;
 using othp::MoveRecord;
 
 // game g leaves the first phase for the second
-__device__ __forceinline__ void park(const ZoneArgs& a, u64 g, const othp::Game& G) {
-    u64 w[othx::kRecordWords];
-    othx::pack(G, g, w);
-    const u64 slot = atomicAdd(a.parked, 1ull);
-    if (slot >= a.n) return;  // (a game parks once, so never: the check keeps a defect inside the list)
-    ulonglong2* r = reinterpret_cast<ulonglong2*>(a.records + slot * othx::kRecordWords);
-    r[0] = make_ulonglong2(w[0], w[1]);
-    r[1] = make_ulonglong2(w[2], w[3]);
-    r[2] = make_ulonglong2(w[4], w[5]);
-}
-
-// THE FIRST PHASE: play.hip's play_body / budget.hip's budget_play_body with
-// the parking step; kOrdered: order_core.hpp's machine, kBudget: by node budget
-template <bool kOrdered, bool kBudget>
-__device__ __forceinline__ void park_body(const ZoneArgs& a) {
-    __shared__ u32 frames[othm::kFrames * othm::kFields * kBlock];
-    __shared__ int tables[2 * othm::kEvalTable];
-    const u32 lane = threadIdx.x;
-    if (lane < (u32)othm::kEvalTable) {
-        othm::widen_weight(a.w[0], (int)lane, tables);
-        othm::widen_weight(a.w[1], (int)lane, tables + othm::kEvalTable);
+struct Park {
+    __device__ __forceinline__ void operator()(const ZoneArgs& a, u64 g, const othp::Game& G) const {
+        u64 w[othx::kRecordWords];
+        othx::pack(G, g, w);
+        const u64 slot = atomicAdd(a.parked, 1ull);
+        if (slot >= a.n) return;  // (a game parks once, so never: the check keeps a defect inside the list)
+        ulonglong2* r = reinterpret_cast<ulonglong2*>(a.records + slot * othx::kRecordWords);
+        r[0] = make_ulonglong2(w[0], w[1]);
+        r[1] = make_ulonglong2(w[2], w[3]);
+        r[2] = make_ulonglong2(w[4], w[5]);
     }
-    __syncthreads();
-    SearchStack stk{frames + lane};
-    othm::Lane L;
-    L.depth = -1;
-    othm::Order Q;  // (unused, and gone, when !kOrdered)
-    othm::order_reset(Q);
-    othb::Deepen D;  // (unused, and gone, when !kBudget)
-    D.d = 0;
-    othp::Game G;
-    G.live = false;
-    MoveRecord rec{nullptr};
-    u64 idx = 0;
-    bool exhausted = false;  // the lane has made its failing request
-    for (;;) {
-        const bool idle = !G.live;
-        const bool want = idle && !exhausted;
-        const u64 wantm = __ballot(want);
-        const u64 busym = __ballot(!idle);
-        if ((wantm | busym) == 0) break;
-        const u64 cnt = (u64)__popcll(wantm);
-        if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
-            u64 base = 0;
-            if (lane == 0) {
-                base = atomicAdd(a.work, cnt);
-                if (base + cnt == a.total) atomicExch(a.work, 0ull);  // every request is made: reset
-            }
-            base = __shfl(base, 0);
-            if (want) {
-                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
-                if (g >= a.n) {
-                    exhausted = true;
-                } else {
-                    u64 black = othp::kOpenBlack, white = othp::kOpenWhite;
-                    bool white_to_move = false;
-                    if (a.start) {
-                        const ulonglong2 b = reinterpret_cast<const ulonglong2*>(a.start)[g];
-                        black = b.x;
-                        white = b.y;
-                        white_to_move = a.start_turn && a.start_turn[g] == OTH_WHITE;
-                    }
-                    rec.row = a.moves ? a.moves + g * OTH_MOVES_STRIDE : nullptr;
-                    rec.pad();
-                    othp::begin(G, L, a.match, othp::game_key(a.seed_state, a.game_id0 + g), black, white,
-                                white_to_move);
-                    D.d = 0;
-                    idx = g;
-                    if (!G.live) emit(a, g, G);  // overlapping boards
-                }
-            }
-        }
-        if (G.live) {
-            if constexpr (kBudget)
-                othb::advance_play<DeviceRules, kOrdered, true>(G, L, Q, D, stk, tables, a.match, a.budgets, rec);
-            else
-                othp::advance<DeviceRules, kOrdered, true>(G, L, Q, stk, tables, a.match, rec);
-            if (!G.live) {
-                if (G.status == othp::kParked)
-                    park(a, idx, G);
-                else
-                    emit(a, idx, G);
-            }
-        }
-    }
-}
+};
 
-__global__ __launch_bounds__(kBlock) void park_fixed_games(ZoneArgs a) { park_body<false, false>(a); }
-__global__ __launch_bounds__(kBlock) void park_ordered_games(ZoneArgs a) { park_body<true, false>(a); }
-__global__ __launch_bounds__(kBlock) void park_budget_games(ZoneArgs a) { park_body<false, true>(a); }
-__global__ __launch_bounds__(kBlock) void park_budget_ordered_games(ZoneArgs a) { park_body<true, true>(a); }
+// THE FIRST PHASE: game_loop.hpp's loop with the parking step, by fixed depth or
+// by node budget (kBudget), either move order (kOrdered)
+__global__ __launch_bounds__(kBlock) void park_fixed_games(ZoneArgs a) {
+    othp::game_body<kBlock, false, false, true>(a, Park{});
+}
+__global__ __launch_bounds__(kBlock) void park_ordered_games(ZoneArgs a) {
+    othp::game_body<kBlock, true, false, true>(a, Park{});
+}
+__global__ __launch_bounds__(kBlock) void park_budget_games(ZoneArgs a) {
+    othp::game_body<kBlock, false, true, true>(a, Park{});
+}
+__global__ __launch_bounds__(kBlock) void park_budget_ordered_games(ZoneArgs a) {
+    othp::game_body<kBlock, true, true, true>(a, Park{});
+}
 
 // THE SECOND PHASE: the parked games, each played to its end by the solver
 __global__ __launch_bounds__(kBlock) void finish_parked_games(ZoneArgs a) {
@@ -215,14 +151,8 @@ __global__ __launch_bounds__(kBlock) void finish_parked_games(ZoneArgs a) {
         if ((wantm | busym) == 0) break;
         const u64 cnt = (u64)__popcll(wantm);
         if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
-            u64 base = 0;
-            if (lane == 0) {
-                base = atomicAdd(a.work, cnt);
-                if (base + cnt == total) atomicExch(a.work, 0ull);  // every request is made: reset
-            }
-            base = __shfl(base, 0);
+            const u64 s = othd::take(a.work, total, wantm, cnt, lane);
             if (want) {
-                const u64 s = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
                 if (s >= n) {
                     exhausted = true;
                 } else {
@@ -284,10 +214,8 @@ int othx_play(const uint64_t* start, const uint8_t* start_turn, uint64_t seed, u
               uint32_t node_limit, uint8_t* a_black, uint64_t* final_boards, int8_t* diff, uint8_t* plies,
               uint8_t* moves, uint8_t* status, uint64_t* nodes, int64_t* hist, void* scratch, int64_t scratch_bytes,
               uint64_t* work, int64_t n, void* stream) {
-    if (order < 0 || order > OTHO_MAX_ORDER) return OTH_EINVAL;
-    if (n < 0 || !work || !weights_a || !weights_b || depth_a < 1 || depth_a > OTHM_MAX_DEPTH || depth_b < 1 ||
-        depth_b > OTHM_MAX_DEPTH || (budget_a == 0) != (budget_b == 0) || solve_empties < 1 ||
-        solve_empties > OTHS_MAX_EMPTIES || n_rand_a < 0 || n_rand_b < 0)
+    if (!othp::game_args_ok(order, n, work, weights_a, weights_b, depth_a, depth_b, n_rand_a, n_rand_b) ||
+        (budget_a == 0) != (budget_b == 0) || solve_empties < 1 || solve_empties > OTHS_MAX_EMPTIES)
         return OTH_EINVAL;
     const int64_t need = othx_scratch_bytes(n);
     if (need < 0 || !scratch || ((uintptr_t)scratch & 15) || scratch_bytes < need) return OTH_EINVAL;
@@ -297,36 +225,13 @@ int othx_play(const uint64_t* start, const uint8_t* start_turn, uint64_t seed, u
     const int grid2 = finish_grid(n);
     if (grid1 <= 0 || grid2 <= 0) return status_of(hipErrorInvalidDevice);
     ZoneArgs a;
-    a.start = start;
-    a.start_turn = start_turn;
-    a.a_black = a_black;
-    a.final_boards = final_boards;
-    a.diff = diff;
-    a.plies = plies;
-    a.moves = moves;
-    a.status = status;
-    a.nodes = nodes;
-    a.hist = reinterpret_cast<unsigned long long*>(hist);
-    a.work = reinterpret_cast<unsigned long long*>(work);
+    othp::fill_game(a, start, start_turn, seed, game_id0, weights_a, weights_b, depth_a, depth_b, solve_empties,
+                    n_rand_a, n_rand_b, swap_colours, node_limit, a_black, final_boards, diff, plies, moves, status,
+                    nodes, hist, work, n, (int64_t)grid1 * kBlock);
     a.parked = reinterpret_cast<unsigned long long*>(scratch);
     a.records = reinterpret_cast<u64*>(scratch) + othx::kCounterWords;
-    a.n = (u64)n;
-    a.total = (u64)n + (u64)grid1 * kBlock;
-    a.seed_state = othp::seed_state(seed);
-    a.game_id0 = game_id0;
-    a.match.depth[0] = depth_a;
-    a.match.depth[1] = depth_b;
-    a.match.n_rand[0] = (u32)std::min(n_rand_a, OTHP_MAX_RANDOM);
-    a.match.n_rand[1] = (u32)std::min(n_rand_b, OTHP_MAX_RANDOM);
-    a.match.exact_empties = solve_empties;
-    a.match.limit = node_limit ? node_limit : OTHM_DEFAULT_NODE_LIMIT;
-    a.match.swap = swap_colours != 0;
     a.budgets.budget[0] = budget_a;
     a.budgets.budget[1] = budget_b;
-    for (int k = 0; k < OTH_EVAL_WEIGHTS; k++) {
-        a.w[0][k] = weights_a[k];
-        a.w[1][k] = weights_b[k];
-    }
     hipStream_t q = (hipStream_t)stream;
     int rc = status_of(hipMemsetAsync(a.parked, 0, OTHX_COUNTER_BYTES, q));
     if (rc != OTH_OK) return rc;

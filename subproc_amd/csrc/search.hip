@@ -11,9 +11,8 @@
 //   * the eval table: oth_eval's int8 [4][9], passed by value with the launch
 //     and widened into LDS (int rows padded to 12) by the block's one wave;
 //   * the refill: idle lanes take the next positions from the caller's work
-//     word, kRefillMin of them at a time by one atomic of lane 0, exactly as
-//     solve.hip does (its header has the contract and the measurement behind
-//     the 8).
+//     word, kRefillMin of them at a time, by device_common.hpp's take()
+//     (solve.hip's header has the measurement behind the 8).
 //
 // search_ordered_kernel is the same loop around order_core.hpp's
 // advance_ordered() (include/othello_order.h, order = 1): the lane's scoring
@@ -94,14 +93,8 @@ __device__ __forceinline__ void search_body(const SearchArgs& a) {
         if ((wantm | busym) == 0) break;
         const u64 cnt = (u64)__popcll(wantm);
         if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
-            u64 base = 0;
-            if (lane == 0) {
-                base = atomicAdd(a.work, cnt);
-                if (base + cnt == a.total) atomicExch(a.work, 0ull);  // every request is made: reset
-            }
-            base = __shfl(base, 0);
+            const u64 g = othd::take(a.work, a.total, wantm, cnt, lane);
             if (want) {
-                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
                 if (g >= a.n) {
                     exhausted = true;
                 } else {

@@ -12,14 +12,12 @@
 //   * the refill: a lane whose position ends takes the next one from the
 //     caller's work word.  The wave's idle lanes are counted by one ballot per
 //     iteration; once kRefillMin of them wait (or nothing else is left to do)
-//     they are served by ONE atomic of lane 0 (their count added), each taking
-//     the slot of its rank.  Every lane makes exactly one failing request, so
-//     the requests of a launch add up to n + lanes; the add that reaches that
-//     sum resets the word to 0 (oth_rollout's contract).  Measured (DESIGN.md
-//     §12, 1M positions at 6 empties / 524k at 8, full grid): refilling each
-//     lane at once 12.4 / 47.9 ms (the one work word saturates: an atomic per
-//     wave nearly every iteration), at 8 idle lanes 4.7 / 48.4 ms, a whole
-//     wave at a time like the rollouts 8.9 / 84.4 ms.
+//     they are served by device_common.hpp's take(), which states the word's
+//     protocol (oth_rollout's contract: 0 at launch, left at 0).  Measured
+//     (DESIGN.md §12, 1M positions at 6 empties / 524k at 8, full grid):
+//     refilling each lane at once 12.4 / 47.9 ms (the one work word saturates:
+//     an atomic per wave nearly every iteration), at 8 idle lanes 4.7 / 48.4
+//     ms, a whole wave at a time like the rollouts 8.9 / 84.4 ms.
 //
 // Geometry: one wave per block.  11 frames x 28 B x 64 lanes = 19.25 KB of LDS
 // per block, eight blocks in a CU's 160 KB: two waves per SIMD, which this
@@ -92,14 +90,8 @@ __global__ __launch_bounds__(kSolveBlock) void solve_kernel(SolveArgs a) {
         if ((wantm | busym) == 0) break;
         const u64 cnt = (u64)__popcll(wantm);
         if (wantm != 0 && ((int)cnt >= a.refill_min || busym == 0)) {
-            u64 base = 0;
-            if (lane == 0) {
-                base = atomicAdd(a.work, cnt);
-                if (base + cnt == a.total) atomicExch(a.work, 0ull);  // every request is made: reset
-            }
-            base = __shfl(base, 0);
+            const u64 g = othd::take(a.work, a.total, wantm, cnt, lane);
             if (want) {
-                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
                 if (g >= a.n) {
                     exhausted = true;
                 } else {
@@ -145,14 +137,8 @@ __global__ __launch_bounds__(kSolveBlock) void solve_windowed(SolveArgs a) {
         if ((wantm | busym) == 0) break;
         const u64 cnt = (u64)__popcll(wantm);
         if (wantm != 0 && ((int)cnt >= a.refill_min || busym == 0)) {
-            u64 base = 0;
-            if (lane == 0) {
-                base = atomicAdd(a.work, cnt);
-                if (base + cnt == a.total) atomicExch(a.work, 0ull);  // every request is made: reset
-            }
-            base = __shfl(base, 0);
+            const u64 g = othd::take(a.work, a.total, wantm, cnt, lane);
             if (want) {
-                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
                 if (g >= a.n) {
                     exhausted = true;
                 } else {

@@ -288,14 +288,8 @@ __global__ __launch_bounds__(kTaskBlock) void task_kernel(TaskArgs a) {
         u64 lim = 0;
         u32 spent = 0;
         if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
-            u64 base = 0;
-            if (lane == 0) {
-                base = atomicAdd(a.work, cnt);
-                if (base + cnt == total) atomicExch(a.work, 0ull);  // every request is made: reset
-            }
-            base = __shfl(base, 0);
+            const u64 g = othd::take(a.work, total, wantm, cnt, lane);
             if (want) {
-                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
                 if (g >= ntasks) {
                     exhausted = true;
                 } else {
@@ -372,14 +366,8 @@ __global__ __launch_bounds__(kTaskBlock) void task_ordered_kernel(TaskArgs a) {
         u64 lim = 0;
         u32 spent = 0;
         if (wantm != 0 && ((int)cnt >= kRefillMin || busym == 0)) {
-            u64 base = 0;
-            if (lane == 0) {
-                base = atomicAdd(a.work, cnt);
-                if (base + cnt == total) atomicExch(a.work, 0ull);  // every request is made: reset
-            }
-            base = __shfl(base, 0);
+            const u64 g = othd::take(a.work, total, wantm, cnt, lane);
             if (want) {
-                const u64 g = base + (u64)__popcll(wantm & ((1ull << lane) - 1ull));
                 if (g >= ntasks) {
                     exhausted = true;
                 } else {

@@ -1,4 +1,4 @@
-"""The work-word launch protocol of ops.py (one statement, nine entry points):
+"""The work-word launch protocol of ops.py (one statement, fourteen entry points):
 a call the library refuses drops the stream's cached word or zeroes the
 caller's, the next good call is the one a fresh stream makes, and a capture
 without a word is refused before anything is launched.
@@ -48,6 +48,17 @@ ENTRY = {
                      lambda sb, st, mb, mt, w: ops.search_moves(mb, mt, 0, work=w)),
     "play": (lambda sb, st, mb, mt, w: ops.play(N, SEED, depth_a=1, depth_b=2, want_nodes=True, work=w),
              lambda sb, st, mb, mt, w: ops.play(N, SEED, depth_a=0, work=w)),
+    "play_ordered": (lambda sb, st, mb, mt, w: ops.play(N, SEED, depth_a=1, depth_b=2, order=1, want_nodes=True, work=w),
+                     lambda sb, st, mb, mt, w: ops.play(N, SEED, depth_a=0, order=1, work=w)),
+    "play_budget": (lambda sb, st, mb, mt, w: ops.play(N, SEED, depth_a=2, budget=(16, 64), want_nodes=True, work=w),
+                    lambda sb, st, mb, mt, w: ops.play(N, SEED, depth_a=0, budget=64, work=w)),
+    "play_solve": (lambda sb, st, mb, mt, w: ops.play(N, SEED, depth_a=1, depth_b=2, solve_empties=6,
+                                                      record_moves=True, want_nodes=True, work=w),
+                   lambda sb, st, mb, mt, w: ops.play(N, SEED, depth_a=0, solve_empties=6, work=w)),
+    "solve_line": (lambda sb, st, mb, mt, w: ops.solve_line(sb, st, max_empties=6, want_nodes=True, work=w),
+                   lambda sb, st, mb, mt, w: ops.solve_line(sb, st, max_empties=13, work=w)),
+    "search_line": (lambda sb, st, mb, mt, w: ops.search_line(mb, mt, 2, want_nodes=True, work=w),
+                    lambda sb, st, mb, mt, w: ops.search_line(mb, mt, 2, order=9, work=w)),
 }
 
 
