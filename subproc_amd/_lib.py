@@ -21,6 +21,7 @@ MOVES_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_moves.h"
 BUDGET_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_budget.h")
 LINE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_line.h")
 PLAY_SOLVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_play_solve.h")
+PERFT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_perft.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -69,6 +70,10 @@ MOVES_SEARCH_SLOTS = 64
 LINE_STRIDE = 32             # include/othello_line.h
 LINE_BADDEPTH = 6
 PLAY_SOLVE_COUNTER_BYTES, PLAY_SOLVE_PARKED_BYTES = 16, 48  # include/othello_play_solve.h
+PERFT_MAX_DEPTH, PERFT_MAX_SPLIT = 14, 8  # include/othello_perft.h
+PERFT_MAX_TASKS, PERFT_ROOT_SLOTS = 1 << 24, 64
+PERFT_COUNTED, PERFT_INVALID, PERFT_LIMIT, PERFT_BADDEPTH = 1, 2, 3, 7
+PERFT_COUNT_LDS_BYTES = 19968
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -216,6 +221,13 @@ PLAY_SOLVE_SIGNATURES = {
     "othx_play_grid": (_I, [_I64, _I, _I]),
 }
 
+# perft, include/othello_perft.h (its own prefix likewise)
+PERFT_SIGNATURES = {
+    "othc_perft": (_I, [_P, _P, _I, _P, _I, ctypes.c_uint32, _P, _P, _P, _P, _P, _I64, _P, _I64, _P]),
+    "othc_perft_scratch_bytes": (_I64, [_I64, _I64]),
+    "othc_perft_grid": (_I, [_I64]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -249,7 +261,8 @@ def load():
     for name, (res, args) in {**SIGNATURES, **SOLVE_SIGNATURES, **SEARCH_SIGNATURES, **PLAY_SIGNATURES,
                               **TREE_SIGNATURES, **ORDER_SIGNATURES, **SOLVE_TREE_SIGNATURES,
                               **SOLVE_HASH_SIGNATURES, **SOLVE_WINDOW_SIGNATURES, **MOVES_SIGNATURES,
-                              **BUDGET_SIGNATURES, **LINE_SIGNATURES, **PLAY_SOLVE_SIGNATURES}.items():
+                              **BUDGET_SIGNATURES, **LINE_SIGNATURES, **PLAY_SOLVE_SIGNATURES,
+                              **PERFT_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -33,6 +33,12 @@ policy into GameRunner unchanged:
                    (depth 1); or the one line "pv unavailable" (policies random
                    and greedy, --split, more than 12 empties in the exact
                    range).  Nothing is played.  Player never sends it.
+  perft D       -> ops.perft of the position at depth D (0..14; a pass is a ply,
+                   a finished game one path): one line "<move> <count>" per legal
+                   move of the side to move in a1..h8 order, then one line with
+                   the total; or the one line "perft unavailable" (D out of
+                   range, a task past its node limit).  Whatever the policy.
+                   Nothing is played.  Player never sends it.
 
 Rules and move generation run on the GPU through the drop-in Board
 (subproc_amd.board); the move choice is the env's policy: "random" (uniform
@@ -288,6 +294,22 @@ class Engine:
         return " ".join(["%d" % int(r.value.cpu()[0])] + [
             "PS" if sq == _lib.PASS else handstr_from_coord(sq & 7, sq >> 3).upper() for sq in line])
 
+    def perft(self, depth):
+        """The `perft D` command's lines: "<move> <count>" for every legal move
+        of the side to move, lowest square first, then the total; or ["perft
+        unavailable"].  The tree's top plies become tasks for the whole device
+        (ops.perft's split: the fastest measured)."""
+        if self.board.turn not in (gboard.Black, gboard.White) or not 0 <= depth <= _lib.PERFT_MAX_DEPTH:
+            return ["perft unavailable"]
+        boards, side, _ = self._position()
+        split = _lib.PERFT_MAX_SPLIT if depth >= 12 else min(max(depth - 3, 1), 7)
+        r = ops.perft(boards, side, depth, split=split, want_divide=True)
+        if int(r.status.cpu()[0]) != _lib.PERFT_COUNTED:
+            return ["perft unavailable"]
+        row = r.divide[0].cpu().tolist()
+        return ["%s %d" % (handstr_from_coord(sq & 7, sq >> 3).upper(), row[sq]) for sq in range(64) if row[sq]] + [
+            "%d" % int(r.leaves.cpu()[0])]
+
     def choose(self):
         b = self.board
         puts = b.puttables(b.turn)
@@ -326,6 +348,11 @@ class Engine:
             out("")
         elif cmd == "pv":
             out(self.pv())
+        elif cmd.split()[:1] == ["perft"]:
+            arg = cmd.split()[1:]
+            ok = len(arg) == 1 and arg[0].isdigit()
+            for t in (self.perft(int(arg[0])) if ok else ["perft unavailable"]):
+                out(t)
         elif cmd == "verbose p":
             extra = " weights=%s" % self.weights.reshape(-1).tolist() if self.policy in ("eval", "search") else ""
             if self.policy == "search":

@@ -131,6 +131,14 @@ class VecEnv:
         return ops.search_line(self.boards, self.turn, depth, weights=weights, order=order, node_limit=node_limit,
                                want_nodes=want_nodes)
 
+    def perft(self, depth, split=0, want_divide=False, want_nodes=False, node_limit=0, max_tasks=1 << 20):
+        """Perft of the current state (ops.perft): per game the number of move
+        paths of length `depth` (a pass is a ply, a finished game one path), with
+        `want_divide` the count below every legal move.  `split` >= 1 spreads
+        each game's tree over the device, for a few games at a time."""
+        return ops.perft(self.boards, self.turn, depth, split=split, want_divide=want_divide, want_nodes=want_nodes,
+                         node_limit=node_limit, max_tasks=max_tasks)
+
     def books(self):
         """Book text (serialize_str, board.py:214-221) of every game: oth_book_text
         on the device, one 67-byte line per game, decoded on the host."""

@@ -878,6 +878,78 @@ def search_moves(boards, turn, depth, weights=None, node_limit=0, want_nodes=Fal
                        work)
 
 
+PerftResult = namedtuple("PerftResult", "leaves divide status nodes")
+
+
+def perft(boards, turn, depth, split=0, want_divide=False, want_nodes=False, node_limit=0, max_tasks=1 << 20,
+          work=None):
+    """Perft (othc_perft, include/othello_perft.h): the number of move paths of
+    length ``depth`` from every position for its mover (White if turn == 2,
+    else Black).  A PASS IS A PLY and a finished game is one path whatever is
+    left of the depth -- the published convention (from the opening 4, 12, 56,
+    244, 1396, ...), not the searches' "a pass costs no depth".  ``depth`` is an
+    int in 0..14 or a uint8 tensor with one depth per position.
+
+    Returns PerftResult(leaves int64, divide int64 (n, 64) or None, status
+    uint8, nodes int64 or None).  ``divide[i, s]`` (with ``want_divide``) is
+    the count below root move s, 0 where s is no move; the row is all 0 at a
+    root pass, a finished game and depth 0, else it sums to ``leaves[i]``.
+    status is _lib.PERFT_COUNTED, PERFT_INVALID (black & white overlap),
+    PERFT_LIMIT (a task ran into ``node_limit``; 0 = the library's default,
+    2**28 positions per task) or PERFT_BADDEPTH (a per-position depth above
+    14); the last three have counts of 0.  The counts stay below 2**62.
+    ``nodes`` (with ``want_nodes``) is the number of positions the counting
+    kernel generated moves for, a diagnostic that depends on ``split``.
+
+    ``split`` = S (0..8) expands every position S plies, level by level on the
+    device, into a list of at most ``max_tasks`` tasks (up to 2**24; 48 bytes
+    of scratch each) that all the device's lanes then count: what spreads ONE
+    position over the device, where split 0 gives it one lane.  A level that
+    does not fit the list is skipped with those after it; leaves, divide and
+    status do not depend on ``split`` or ``max_tasks``.  ``want_divide`` needs
+    the root moves as tasks: it raises ``split`` to at least 1 and
+    ``max_tasks`` to at least 64 per position.
+
+    Argument checks and ``work`` as in :func:`search`.  The scratch is
+    allocated here (the caching allocator's memory, no synchronisation) and
+    nothing is read on the host, so the call may be captured in a graph with an
+    explicit work word -- the scratch then belongs to the graph's pool.
+    """
+    n = _n(boards)
+    d = boards.device
+    pb = _dev(boards, "boards", torch.int64)
+    pt = _dev(turn, "turn", torch.uint8, (n,), d)
+    _capturing("perft", work)
+    _check32("node_limit", int(node_limit))
+    if isinstance(depth, torch.Tensor):
+        pd, scalar = _dev(depth, "depth", torch.uint8, (n,), d), 0
+    else:
+        pd, scalar = None, int(depth)
+        if not 0 <= scalar <= _lib.PERFT_MAX_DEPTH:
+            raise ValueError(f"depth must lie in 0..{_lib.PERFT_MAX_DEPTH}")
+    split, max_tasks = int(split), int(max_tasks)
+    if not 0 <= split <= _lib.PERFT_MAX_SPLIT:
+        raise ValueError(f"split must lie in 0..{_lib.PERFT_MAX_SPLIT}")
+    if not 0 <= max_tasks <= _lib.PERFT_MAX_TASKS:
+        raise ValueError(f"max_tasks must lie in 0..{_lib.PERFT_MAX_TASKS}")
+    if want_divide:
+        split, max_tasks = max(split, 1), max(max_tasks, _lib.PERFT_ROOT_SLOTS * n)
+    lib = _lib.load()
+    size = lib.othc_perft_scratch_bytes(n, max_tasks)
+    if size < 0:
+        check(int(size), "othc_perft_scratch_bytes")
+    leaves = torch.empty(n, dtype=torch.int64, device=d)
+    divide = torch.empty((n, 64), dtype=torch.int64, device=d) if want_divide else None
+    status = torch.empty(n, dtype=torch.uint8, device=d)
+    nodes = torch.empty(n, dtype=torch.int64, device=d) if want_nodes else None
+    scratch = torch.empty(max(int(size), 16) // 8, dtype=torch.int64, device=d)
+    _launch("othc_perft", lib.othc_perft, (pb, pt, scalar, pd, split, int(node_limit), leaves.data_ptr(), _ptr(divide),
+                                           status.data_ptr(), _ptr(nodes), scratch.data_ptr(), scratch.numel() * 8,
+                                           _work_ptr(work, d), n), work, d)
+    # (the caching allocator hands the scratch to later work of THIS stream only)
+    return PerftResult(leaves, divide, status, nodes)
+
+
 LineResult = namedtuple("LineResult", "line length value best_move status nodes end_boards end_turn")
 
 
@@ -1212,6 +1284,7 @@ __all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", 
            "search_budget", "BudgetResult",
            "solve_moves", "search_moves", "MovesResult",
            "solve_line", "search_line", "LineResult",
+           "perft", "PerftResult",
            "sample_midgame",
            "replay",
            "book_text", "features", "evaluate", "to_numpy_u64", "from_numpy_u64",
