@@ -22,6 +22,7 @@ BUDGET_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_budget.
 LINE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_line.h")
 PLAY_SOLVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_play_solve.h")
 PERFT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_perft.h")
+MCTS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_mcts.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -74,6 +75,9 @@ PERFT_MAX_DEPTH, PERFT_MAX_SPLIT = 14, 8  # include/othello_perft.h
 PERFT_MAX_TASKS, PERFT_ROOT_SLOTS = 1 << 24, 64
 PERFT_COUNTED, PERFT_INVALID, PERFT_LIMIT, PERFT_BADDEPTH = 1, 2, 3, 7
 PERFT_COUNT_LDS_BYTES = 19968
+MCTS_MAX_ITERATIONS, MCTS_MAX_NODES = 65536, 1 << 20  # include/othello_mcts.h
+MCTS_MAX_BLOCKS, MCTS_NODE_BYTES, MCTS_PATH_ENTRIES, MCTS_LDS_BYTES = 4096, 32, 132, 6672
+MCTS_SEARCHED, MCTS_INVALID, MCTS_NO_MOVE = 1, 2, 255
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -228,6 +232,14 @@ PERFT_SIGNATURES = {
     "othc_perft_grid": (_I, [_I64]),
 }
 
+# the Monte Carlo tree search, include/othello_mcts.h (its own prefix likewise)
+MCTS_SIGNATURES = {
+    "othu_mcts": (_I, [_P, _P, _I, ctypes.c_float, _P, _U64, _U64, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64,
+                       _P]),
+    "othu_mcts_scratch_bytes": (_I64, [_I64, _I]),
+    "othu_mcts_grid": (_I, [_I64]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -262,7 +274,7 @@ def load():
                               **TREE_SIGNATURES, **ORDER_SIGNATURES, **SOLVE_TREE_SIGNATURES,
                               **SOLVE_HASH_SIGNATURES, **SOLVE_WINDOW_SIGNATURES, **MOVES_SIGNATURES,
                               **BUDGET_SIGNATURES, **LINE_SIGNATURES, **PLAY_SOLVE_SIGNATURES,
-                              **PERFT_SIGNATURES}.items():
+                              **PERFT_SIGNATURES, **MCTS_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -77,6 +77,11 @@ gives every ``go`` a budget of B nodes instead of a fixed depth: the move is
 ops.search_budget's, an iterative deepening whose deepest completed iteration
 answers, ``--depth`` (at most 8) being its cap; "verbose 1" then shows the depth
 the last search reached at the end of the board display's last line.
+``--policy mcts --iterations T`` (T = 1..65536; ``--explore C``, default 0.5)
+needs no eval table: every ``go`` is one ops.mcts call on the position, a Monte
+Carlo tree search of T iterations of 64 random playouts, and plays its most
+visited move.  The playouts are ``--seed``'s games; the k-th ``go`` (from 0)
+takes the ids from k * T * 64, so no two ``go``s share a playout.
 """
 import argparse
 import random
@@ -92,7 +97,8 @@ from .codec import handstr_from_coord
 
 class Engine:
     def __init__(self, name="GPU", policy="greedy", seed=0, weights=None, solve_empties=0, depth=1, split=0, order=0,
-                 solve_task_empties=None, solve_order=None, solve_hash_bits=None, solve_wld_empties=0, nodes=None):
+                 solve_task_empties=None, solve_order=None, solve_hash_bits=None, solve_wld_empties=0, nodes=None,
+                 iterations=None, explore=0.5):
         top = _lib.SOLVE_MAX_EMPTIES if solve_task_empties is None else _lib.SOLVE_TREE_MAX_EMPTIES
         if not 0 <= solve_empties <= top:
             raise ValueError(f"solve_empties must lie in 0..{top}" + (
@@ -127,6 +133,15 @@ class Engine:
                 raise ValueError("nodes must lie in 1..2**32 - 1")
             if depth > _lib.SEARCH_MAX_DEPTH:
                 raise ValueError(f"with nodes, depth is the cap and must lie in 1..{_lib.SEARCH_MAX_DEPTH}")
+        if policy == "mcts":
+            if iterations is None or not 1 <= iterations <= _lib.MCTS_MAX_ITERATIONS:
+                raise ValueError(f"policy mcts needs iterations in 1..{_lib.MCTS_MAX_ITERATIONS}")
+        elif iterations is not None:
+            raise ValueError("iterations applies to policy mcts")
+        self.iterations = iterations
+        self.explore = float(explore)
+        self.seed = seed
+        self.go_index = 0  # the searches made so far: each takes its own playout ids
         self.nodes = nodes
         self.reached = None  # the depth the last budget search reached
         self.solve_empties = solve_empties
@@ -219,6 +234,18 @@ class Engine:
                            order=self.order)
         sq = int(r.best_move.cpu()[0])
         if int(r.status.cpu()[0]) != _lib.SEARCH_SEARCHED or sq > 63:
+            return None
+        return handstr_from_coord(sq & 7, sq >> 3)
+
+    def _choose_mcts(self):
+        """The Monte Carlo tree search's move for the side to move (one
+        othu_mcts launch), or None when it gives none."""
+        boards, side, _ = self._position()
+        r = ops.mcts(boards, side, self.iterations, explore=self.explore, seed=self.seed,
+                     game_id0=self.go_index * self.iterations * 64)
+        self.go_index += 1
+        sq = int(r.best_move.cpu()[0])
+        if int(r.status.cpu()[0]) != _lib.MCTS_SEARCHED or sq > 63:
             return None
         return handstr_from_coord(sq & 7, sq >> 3)
 
@@ -326,6 +353,10 @@ class Engine:
             mv = self._choose_searched()
             if mv is not None:
                 return mv
+        if self.policy == "mcts" and b.turn in (gboard.Black, gboard.White):
+            mv = self._choose_mcts()
+            if mv is not None:
+                return mv
         if self.policy in ("eval", "search"):  # (search: its LIMIT / NOROOM fall-back)
             return self._choose_eval(puts)
         return self._choose_greedy(puts)
@@ -355,6 +386,8 @@ class Engine:
                 out(t)
         elif cmd == "verbose p":
             extra = " weights=%s" % self.weights.reshape(-1).tolist() if self.policy in ("eval", "search") else ""
+            if self.policy == "mcts":
+                extra = " iterations=%d explore=%g" % (self.iterations, self.explore)
             if self.policy == "search":
                 extra = " depth=%d" % self.depth + (" nodes=%d" % self.nodes if self.nodes is not None else "") + (
                     " split=%d" % self.split if self.split > 0 else "") + (
@@ -402,7 +435,7 @@ class Engine:
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     p.add_argument("--name", default="GPU")
-    p.add_argument("--policy", choices=["random", "greedy", "eval", "search"], default="greedy")
+    p.add_argument("--policy", choices=["random", "greedy", "eval", "search", "mcts"], default="greedy")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--params", default=None, help="eval table in the paramgen.py file format (policies eval and search)")
     p.add_argument("--depth", type=int, default=1, metavar="D", help="plies policy search looks ahead (1..8, with --split S 1..8+S)")
@@ -425,12 +458,20 @@ def main(argv=None):
     p.add_argument("--solve-wld-empties", type=int, default=0, metavar="W",
                    help="with more than K and at most W empty squares, solve for win / draw / loss and play the proved "
                         "winning or drawing move (0 = never; W > K, max 12, max 16 with --solve-task-empties)")
+    p.add_argument("--iterations", type=int, default=None, metavar="T",
+                   help="policy mcts: iterations of 64 random playouts per go (1..65536)")
+    p.add_argument("--explore", type=float, default=0.5, metavar="C", help="policy mcts: UCT's exploration constant")
     a = p.parse_args(argv)
+    if a.policy == "mcts" and a.iterations is None:
+        p.error("--policy mcts needs --iterations")
+    if a.policy != "mcts" and a.iterations is not None:
+        p.error("--iterations applies to --policy mcts")
     if a.solve_hash_bits is not None and a.solve_task_empties is None:
         p.error("--solve-hash-bits needs --solve-task-empties")
     weights = params.read_paramgen(a.params)[1] if a.params else None
     eng = Engine(a.name, a.policy, a.seed, weights, a.solve_empties, a.depth, a.split, a.order,
-                 a.solve_task_empties, a.solve_order, a.solve_hash_bits, a.solve_wld_empties, a.nodes)
+                 a.solve_task_empties, a.solve_order, a.solve_hash_bits, a.solve_wld_empties, a.nodes, a.iterations,
+                 a.explore)
 
     def out(s):
         sys.stdout.write(s + "\n")

@@ -139,6 +139,13 @@ class VecEnv:
         return ops.perft(self.boards, self.turn, depth, split=split, want_divide=want_divide, want_nodes=want_nodes,
                          node_limit=node_limit, max_tasks=max_tasks)
 
+    def mcts(self, iterations, explore=0.5, seed=0, game_id0=0, max_nodes=None, log_table=None, want_nodes=False):
+        """Monte Carlo tree search from the current state (ops.mcts): per game
+        `iterations` iterations of 64 random playouts, the visits, half-points
+        and disc sums of every root move and the most visited move."""
+        return ops.mcts(self.boards, self.turn, iterations, explore=explore, seed=seed, game_id0=game_id0,
+                        max_nodes=max_nodes, log_table=log_table, want_nodes=want_nodes)
+
     def books(self):
         """Book text (serialize_str, board.py:214-221) of every game: oth_book_text
         on the device, one 67-byte line per game, decoded on the host."""

@@ -950,6 +950,100 @@ def perft(boards, turn, depth, split=0, want_divide=False, want_nodes=False, nod
     return PerftResult(leaves, divide, status, nodes)
 
 
+MctsResult = namedtuple("MctsResult", "visits wins diffs root_wins root_diffs best_move status nodes")
+
+_LOG_TABLES = {}
+
+
+def mcts_log_table(iterations):
+    """The table :func:`mcts` hands the library: float32 ln(max(k, 1)) for k =
+    0..iterations, computed in float64 and rounded once (numpy, host)."""
+    T = int(iterations)
+    if not 1 <= T <= _lib.MCTS_MAX_ITERATIONS:
+        raise ValueError(f"iterations must lie in 1..{_lib.MCTS_MAX_ITERATIONS}")
+    return np.log(np.arange(T + 1, dtype=np.float64).clip(1)).astype(np.float32)
+
+
+def _log_table_on(T, d):
+    """mcts_log_table(T) on device d: uploaded once, cached per (T, device)."""
+    key = (T, d.index)
+    t = _LOG_TABLES.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ops.mcts under graph capture needs its table on the device before the capture: pass "
+                               "log_table, or make one eager call with these iterations first")
+        t = _LOG_TABLES[key] = torch.from_numpy(mcts_log_table(T)).to(d)
+    return t
+
+
+def mcts(boards, turn, iterations, explore=0.5, seed=0, game_id0=0, max_nodes=None, log_table=None, want_nodes=False):
+    """Monte Carlo tree search (othu_mcts, include/othello_mcts.h): UCT over
+    uniform random playouts, ``iterations`` = T (1..65536) iterations of 64
+    playouts from every position for its mover (White if turn == 2, else
+    Black), one wave per tree.  It needs no evaluation function.
+
+    Returns MctsResult(visits int32 (n, 64), wins int32 (n, 64), diffs int32
+    (n, 64), root_wins int32, root_diffs int32, best_move uint8, status uint8,
+    nodes int32 or None).  ``visits[i, s]``, ``wins[i, s]`` and ``diffs[i, s]``
+    are the iterations that went through root move s, the half-points of their
+    playouts for the root mover (2 a win, 1 a draw: at most 128 per visit) and
+    the sum of their final disc differences for the root mover; 0 where s is no
+    move.  ``root_wins``, ``root_diffs`` are the same over all T iterations:
+    ``root_wins / (128 * T)`` estimates the position's value for its mover.
+    ``best_move`` is the move with the most visits (ties: more wins, then the
+    lowest square), 64 where the mover must pass, 255 where the game is over;
+    ``status`` _lib.MCTS_SEARCHED, or MCTS_INVALID (black & white overlap:
+    everything 0, move 255).  ``nodes`` (with ``want_nodes``) counts the tree's
+    nodes, at most ``max_nodes`` (1..2**20, default 1 + 16 T or 2**20): a tree that is
+    full stops growing and goes on playing out from its leaves.
+
+    ``explore`` is UCT's constant c in mean + c sqrt(ln n_parent / n_child),
+    float32 with every operation rounded on its own.  Playout j of iteration t
+    of position i is the game of global id ``game_id0 + (i T + t) 64 + j`` of
+    ``seed`` (ops.rollout's games from the leaf), so the answer is a function
+    of the arguments alone, and row i of a batch is the single call on
+    position i with ``game_id0 + i T 64``.  ``log_table`` (float32 (T + 1,)
+    device tensor) replaces :func:`mcts_log_table`'s values; the default table
+    is uploaded once per (T, device).
+
+    There is no work word.  The scratch (32 B per node for at most 4096 trees
+    at a time) is allocated here (the caching allocator's memory, no
+    synchronisation) and nothing is read on the host, so with the table on the
+    device (``log_table`` passed in, or an earlier call with this T) the call
+    may be captured in a graph -- the scratch then belongs to the graph's pool.
+    """
+    T = int(iterations)
+    if not 1 <= T <= _lib.MCTS_MAX_ITERATIONS:
+        raise ValueError(f"iterations must lie in 1..{_lib.MCTS_MAX_ITERATIONS}")
+    M = min(1 + 16 * T, _lib.MCTS_MAX_NODES) if max_nodes is None else int(max_nodes)
+    if not 1 <= M <= _lib.MCTS_MAX_NODES:
+        raise ValueError(f"max_nodes must lie in 1..{_lib.MCTS_MAX_NODES}")
+    c = float(explore)
+    if not abs(c) <= 3.0e38:
+        raise ValueError("explore must be a finite float32")
+    n = _n(boards)
+    d = boards.device
+    pb = _dev(boards, "boards", torch.int64)
+    pt = _dev(turn, "turn", torch.uint8, (n,), d)
+    table = _log_table_on(T, d) if log_table is None else log_table
+    plt = _dev(table, "log_table", torch.float32, (T + 1,), d)
+    lib = _lib.load()
+    size = lib.othu_mcts_scratch_bytes(n, M)
+    if size < 0:
+        check(int(size), "othu_mcts_scratch_bytes")
+    rows = [torch.empty((n, 64), dtype=torch.int32, device=d) for _ in range(3)]
+    root = [torch.empty(n, dtype=torch.int32, device=d) for _ in range(2)]
+    mv, st = (torch.empty(n, dtype=torch.uint8, device=d) for _ in range(2))
+    nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
+    scratch = torch.empty(max(int(size), 16) // 8, dtype=torch.int64, device=d)
+    with torch.cuda.device(d):
+        check(lib.othu_mcts(pb, pt, T, c, plt, int(seed) & (2**64 - 1), int(game_id0) & (2**64 - 1), M,
+                            *(r.data_ptr() for r in rows), *(r.data_ptr() for r in root), mv.data_ptr(), st.data_ptr(),
+                            _ptr(nd), scratch.data_ptr(), scratch.numel() * 8, n, _stream()), "othu_mcts")
+    # (the caching allocator hands the scratch to later work of THIS stream only)
+    return MctsResult(*rows, *root, mv, st, nd)
+
+
 LineResult = namedtuple("LineResult", "line length value best_move status nodes end_boards end_turn")
 
 
@@ -1285,6 +1379,7 @@ __all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", 
            "solve_moves", "search_moves", "MovesResult",
            "solve_line", "search_line", "LineResult",
            "perft", "PerftResult",
+           "mcts", "mcts_log_table", "MctsResult",
            "sample_midgame",
            "replay",
            "book_text", "features", "evaluate", "to_numpy_u64", "from_numpy_u64",

@@ -1,0 +1,214 @@
+// mcts_host.cpp — the Monte Carlo tree search (include/othello_mcts.h,
+// DESIGN.md §28) on the host: the very walk the device runs
+// (mcts_core.hpp's search(): score, child choice, expansion test, back-up) with
+// a plain C++ statement of the rules, arrays for the tree, loops for the wave's
+// collectives and a plain C++ random playout over DESIGN.md §4's draws.
+//
+// Two uses, as perft_host.cpp's:
+//   * the rule's code can be run under -fsanitize=address,undefined and compared
+//     against tests/mcts_ref.py before any GPU run;
+//   * with threads it is the host baseline of tools/mcts_bench.py.
+//
+// build:  g++ -O2 -std=c++17 -ffp-contract=off -fopenmp -o tools/diag/mcts_host tools/diag/mcts_host.cpp
+//         (-O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all)
+// run:    mcts_host IN OUT iterations explore_bits seed game_id0 max_nodes [threads=16]
+//   IN : one position per line, "<black hex> <white hex> <turn>", and the
+//        table as iterations + 1 lines "L <float32 bits hex>" in order
+//   explore_bits: the exploration constant's float32 bits, hex
+//   OUT: one line per position, "<status> <best_move> <nodes> <root_wins>
+//        <root_diffs>", then the 64 visits, the 64 wins and the 64 diffs; then
+//        one line "plies <env-steps of all playouts> wave_plies <the sum over
+//        the iterations of their longest game>"
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../subproc_amd/csrc/mcts_core.hpp"
+#include "../../subproc_amd/csrc/play_core.hpp"  // DESIGN.md §4's draws: seed_state, game_key, Rng
+#include "host_rules.hpp"
+
+typedef uint64_t u64;
+typedef uint32_t u32;
+
+struct Rules : HostRules {
+    static u32 kth(u64 m, u32 k) {
+        for (; k; k--) m &= m - 1;
+        return lowest(m);
+    }
+};
+
+// one uniformly random game from (P to move, O); the final disc difference from O's side
+static int play_out(u64 P, u64 O, u64 key, u64* plies) {
+    othp::Rng rng;
+    rng.init(key);
+    bool flipped = false;  // P is the leaf's other side
+    for (;;) {
+        const u64 legal = Rules::moves(P, O);
+        if (legal) {
+            const u32 sq = Rules::kth(legal, rng.pick((u32)Rules::count(legal)));
+            const u64 f = Rules::flips(sq, P, O);
+            P |= f | (1ull << sq);
+            O &= ~f;
+        } else if (Rules::moves(O, P) == 0) {
+            break;
+        }
+        ++*plies;  // (a pass is an env-step too)
+        const u64 x = P;
+        P = O;
+        O = x;
+        flipped = !flipped;
+    }
+    const int d = Rules::count(O) - Rules::count(P);
+    return flipped ? -d : d;
+}
+
+struct HostTree {
+    std::vector<u64> P, O;
+    std::vector<u32> nn, ss, link_;
+    std::vector<int> dd;
+    explicit HostTree(u32 M) : P(M), O(M), nn(M), ss(M), link_(M), dd(M) {}
+    void pos(u32 v, u64& p, u64& o) const { p = P.at(v), o = O.at(v); }
+    void set_pos(u32 v, u64 p, u64 o) { P.at(v) = p, O.at(v) = o; }
+    void visits_wins(u32 v, u32& n, u32& s) const { n = nn.at(v), s = ss.at(v); }
+    u32 n(u32 v) const { return nn.at(v); }
+    int d(u32 v) const { return dd.at(v); }
+    u32 link(u32 v) const { return link_.at(v); }
+    void set_stats(u32 v, u32 n, u32 s, int d) { nn.at(v) = n, ss.at(v) = s, dd.at(v) = d; }
+    void set_link(u32 v, u32 l) { link_.at(v) = l; }
+    void add_stats(u32 v, u32 n, u32 s, int d) { nn.at(v) += n, ss.at(v) += s, dd.at(v) += d; }
+    void sync() const {}
+};
+
+struct HostWave {
+    u32 path[othu::kPathEntries];
+    u64 plies = 0;       // env-steps of the playouts (the bench's count)
+    u64 wave_plies = 0;  // the longest game of every iteration: what 64 games in lockstep wait for
+    template <class F>
+    void each(u32 count, F f) const {
+        for (u32 k = 0; k < count; k++) f(k);
+    }
+    template <class F>
+    u32 pick(u32 cnt, F f) const {
+        u32 best = 0;
+        float best_score = 0;
+        for (u32 k = 0; k < cnt; k++) {
+            bool fresh = false;
+            float sc = 0;
+            f(k, fresh, sc);
+            if (fresh) return k;
+            if (k == 0 || othu::better(sc, k, best_score, best)) best = k, best_score = sc;
+        }
+        return best;
+    }
+    void path_set(u32 k, u32 v) {
+        if (k < othu::kPathEntries) path[k] = v;
+    }
+    u32 path_get(u32 k) const { return path[k < othu::kPathEntries ? k : 0]; }
+    void sync() const {}
+    void playout(u64 P, u64 O, u64 id0, u64 seed_state, u32& W, int& D) {
+        W = 0, D = 0;
+        u64 longest = 0;
+        for (u32 j = 0; j < othu::kLanes; j++) {
+            u64 len = 0;
+            const int dp = play_out(P, O, othp::game_key(seed_state, id0 + j), &len);
+            W += othu::half_points(dp);
+            D += dp;
+            plies += len;
+            if (len > longest) longest = len;
+        }
+        wave_plies += longest;
+    }
+};
+
+struct Pos {
+    u64 black, white;
+    int turn;
+};
+struct Row {
+    u32 status = othu::kInvalid, best = othu::kNoMove, nodes = 0, root_wins = 0;
+    int root_diffs = 0;
+    u32 visits[64] = {}, wins[64] = {};
+    int diffs[64] = {};
+};
+
+int main(int argc, char** argv) {
+    if (argc < 8) {
+        fprintf(stderr, "usage: %s IN OUT iterations explore_bits seed game_id0 max_nodes [threads=16]\n", argv[0]);
+        return 2;
+    }
+    const long T = atol(argv[3]);
+    const u32 cbits = (u32)strtoul(argv[4], nullptr, 16);
+    const u64 seed = strtoull(argv[5], nullptr, 0), game_id0 = strtoull(argv[6], nullptr, 0);
+    const long M = atol(argv[7]);
+    const int threads = argc > 8 ? atoi(argv[8]) : 16;
+    if (T < 1 || T > (long)othu::kMaxIterations || M < 1 || M > (long)othu::kMaxNodes || threads < 1) return 2;
+    float c;
+    memcpy(&c, &cbits, 4);
+    FILE* in = fopen(argv[1], "r");
+    if (!in) return 1;
+    std::vector<Pos> pos;
+    std::vector<float> table;
+    char line[256];
+    while (fgets(line, sizeof line, in)) {
+        unsigned long long b, w;
+        unsigned bits;
+        int t;
+        if (sscanf(line, "L %x", &bits) == 1) {
+            float f;
+            memcpy(&f, &bits, 4);
+            table.push_back(f);
+        } else if (sscanf(line, "%llx %llx %d", &b, &w, &t) == 3) {
+            pos.push_back(Pos{b, w, t});
+        }
+    }
+    fclose(in);
+    if ((long)table.size() != T + 1) return 2;
+    const long n = (long)pos.size();
+    std::vector<Row> rows(n);
+    othu::Params p;
+    p.iterations = (u32)T;
+    p.max_nodes = (u32)M;
+    p.explore = c;
+    p.log_table = table.data();
+    p.seed_state = othp::seed_state(seed);
+    p.game_id0 = game_id0;
+    u64 plies = 0, wave_plies = 0;
+    (void)threads;
+#pragma omp parallel for schedule(dynamic, 1) num_threads(threads) reduction(+ : plies, wave_plies)
+    for (long i = 0; i < n; i++) {
+        const Pos& q = pos[i];
+        Row& r = rows[i];
+        if (q.black & q.white) continue;
+        const bool white = q.turn == 2;
+        const u64 P = white ? q.white : q.black, O = white ? q.black : q.white;
+        HostTree tree((u32)M);
+        HostWave wave;
+        r.nodes = othu::search<Rules>(tree, wave, P, O, (u64)i, p);
+        plies += wave.plies;
+        wave_plies += wave.wave_plies;
+        const u64 legal = Rules::moves(P, O);
+        u64 best = 0;
+        for (u32 sq = 0; sq < 64; sq++) {
+            const u64 key = othu::root_entry<Rules>(tree, legal, sq, r.visits[sq], r.wins[sq], r.diffs[sq]);
+            if (key > best) best = key;
+        }
+        r.best = othu::best_move_of<Rules>(best, P, O);
+        r.root_wins = 128u * tree.n(0) - tree.ss[0];
+        r.root_diffs = -tree.d(0);
+        r.status = othu::kSearched;
+    }
+    FILE* o = fopen(argv[2], "w");
+    if (!o) return 1;
+    for (long i = 0; i < n; i++) {
+        const Row& r = rows[i];
+        fprintf(o, "%u %u %u %u %d", r.status, r.best, r.nodes, r.root_wins, r.root_diffs);
+        for (int s = 0; s < 64; s++) fprintf(o, " %u", r.visits[s]);
+        for (int s = 0; s < 64; s++) fprintf(o, " %u", r.wins[s]);
+        for (int s = 0; s < 64; s++) fprintf(o, " %d", r.diffs[s]);
+        fprintf(o, "\n");
+    }
+    fprintf(o, "plies %llu wave_plies %llu\n", (unsigned long long)plies, (unsigned long long)wave_plies);
+    fclose(o);
+    return 0;
+}
