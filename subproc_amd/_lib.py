@@ -23,6 +23,7 @@ LINE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_line.h")
 PLAY_SOLVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_play_solve.h")
 PERFT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_perft.h")
 MCTS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_mcts.h")
+MCTS_TREE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_mcts_tree.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -78,6 +79,8 @@ PERFT_COUNT_LDS_BYTES = 19968
 MCTS_MAX_ITERATIONS, MCTS_MAX_NODES = 65536, 1 << 20  # include/othello_mcts.h
 MCTS_MAX_BLOCKS, MCTS_NODE_BYTES, MCTS_PATH_ENTRIES, MCTS_LDS_BYTES = 4096, 32, 132, 6672
 MCTS_SEARCHED, MCTS_INVALID, MCTS_NO_MOVE = 1, 2, 255
+MCTS_TREE_RECORD_BYTES, MCTS_TREE_LDS_BYTES = 32, 6672  # include/othello_mcts_tree.h
+MCTS_TREE_READY, MCTS_TREE_INVALID, MCTS_TREE_BADMOVE, MCTS_TREE_KEEP = 1, 2, 8, 255
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -240,6 +243,20 @@ MCTS_SIGNATURES = {
     "othu_mcts_grid": (_I, [_I64]),
 }
 
+# the Monte Carlo search trees that persist, include/othello_mcts_tree.h (its own prefix likewise): every call ends
+# in slabs, slab_bytes, records, record_bytes, n, stream
+_TREES = [_P, _I64, _P, _I64, _I64, _P]
+_TREE_ROWS = [_P] * 11
+MCTS_TREE_SIGNATURES = {
+    "othr_trees_slab_bytes": (_I64, [_I64, _I]),
+    "othr_trees_record_bytes": (_I64, [_I64]),
+    "othr_trees_grid": (_I, [_I64]),
+    "othr_init": (_I, [_P, _P, _P, _U64, _U64, _I, *_TREES]),
+    "othr_search": (_I, [_I, _P, ctypes.c_float, _P, _U64, _I, *_TREE_ROWS, *_TREES]),
+    "othr_rows": (_I, [_I, *_TREE_ROWS, *_TREES]),
+    "othr_advance": (_I, [_P, _I, _I, _P, *_TREES]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -274,7 +291,7 @@ def load():
                               **TREE_SIGNATURES, **ORDER_SIGNATURES, **SOLVE_TREE_SIGNATURES,
                               **SOLVE_HASH_SIGNATURES, **SOLVE_WINDOW_SIGNATURES, **MOVES_SIGNATURES,
                               **BUDGET_SIGNATURES, **LINE_SIGNATURES, **PLAY_SOLVE_SIGNATURES,
-                              **PERFT_SIGNATURES, **MCTS_SIGNATURES}.items():
+                              **PERFT_SIGNATURES, **MCTS_SIGNATURES, **MCTS_TREE_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

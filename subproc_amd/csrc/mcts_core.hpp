@@ -2,9 +2,11 @@
 // (include/othello_mcts.h) as code, written once for the device (mcts.hip) and
 // the host (tools/diag/mcts_host.cpp): the selection score and its order, the
 // child choice, the expansion test, the children, the back-up, the rows and
-// the root's best move, and the ids of an iteration's playouts.
+// the root's best move, and the ids of an iteration's playouts; and, for the
+// trees that persist (include/othello_mcts_tree.h, mcts_tree.hip,
+// tools/diag/mcts_tree_host.cpp), the re-rooting.
 //
-// search<R, A, K>() is the walk over one tree.  R are the rules (moves, flips,
+// search<R, A, K>() is the walk over one tree: init_root() and iterate().  R are the rules (moves, flips,
 // lowest, count, kth), A is the tree's memory, K the wave:
 //   A  pos / set_pos, visits_wins, n, d, link and their setters, add_stats, and
 //      sync(): what lies between one phase's writes and the next phase's reads
@@ -115,19 +117,27 @@ struct Params {
     u64 seed_state, game_id0;
 };
 
-// One tree: `iterations` iterations from the root (P to move, O), the position
-// of index i.  Every lane of K calls it with the same arguments.  Returns the
-// number of nodes made.
-template <class R, class A, class K>
-OTHU_FN u32 search(A& tree, K& wave, u64 rootP, u64 rootO, u64 i, const Params& p) {
+// The root alone: node 0 = (P to move, O) with n = s = d = 0 and no children.
+// Ends in a sync.
+template <class A, class K>
+OTHU_FN void init_root(A& tree, K& wave, u64 rootP, u64 rootO) {
     wave.each(1u, [&](u32) {
         tree.set_pos(0u, rootP, rootO);
         tree.set_stats(0u, 0u, 0u, 0);
         tree.set_link(0u, 0u);
     });
     tree.sync();
-    u32 nodes = 1;
-    for (u32 t = 0; t < p.iterations; t++) {
+}
+
+// `count` more iterations of steps 1 to 4 on a tree that holds `nodes` nodes.
+// Iteration t = 0 .. count-1 plays the games of global ids
+// id_base + (first + t) * 64 + lane (modulo 2^64); log_table has entries
+// 0..table_last.  Every lane of K calls it with the same arguments.  Returns
+// the tree's node count afterwards.  Ends in a sync.
+template <class R, class A, class K>
+OTHU_FN u32 iterate(A& tree, K& wave, u64 id_base, u64 first_iteration, u32 count, u32 nodes, u32 table_last,
+                    const Params& p) {
+    for (u32 t = 0; t < count; t++) {
         // 1. select
         u32 v = 0, depth = 0;
         wave.path_set(0u, 0u);
@@ -136,7 +146,7 @@ OTHU_FN u32 search(A& tree, K& wave, u64 rootP, u64 rootO, u64 i, const Params& 
             const u32 cnt = link_cnt(link), first = link_first(link);
             if (cnt == 0 || depth + 2u >= kPathEntries) break;  // (a path never gets that long: header)
             const u32 n_v = tree.n(v);
-            const float log_nv = p.log_table[n_v <= p.iterations ? n_v : p.iterations];  // (n_v <= t)
+            const float log_nv = p.log_table[n_v <= table_last ? n_v : table_last];  // (n_v never passes it)
             const u32 k = wave.pick(cnt, [&](u32 c, bool& fresh, float& sc) {
                 u32 n_c, s_c;
                 tree.visits_wins(first + c, n_c, s_c);
@@ -171,7 +181,7 @@ OTHU_FN u32 search(A& tree, K& wave, u64 rootP, u64 rootO, u64 i, const Params& 
         // 3. play out
         u32 W;
         int D;
-        wave.playout(P, O, playout_id0(p.game_id0, i, p.iterations, t), p.seed_state, W, D);
+        wave.playout(P, O, id_base + (first_iteration + (u64)t) * (u64)kLanes, p.seed_state, W, D);
         // 4. back up: a path's nodes are distinct, so each is one lane's
         tree.sync();
         wave.sync();
@@ -183,6 +193,98 @@ OTHU_FN u32 search(A& tree, K& wave, u64 rootP, u64 rootO, u64 i, const Params& 
         wave.sync();
     }
     return nodes;
+}
+
+// One tree: `iterations` iterations from the root (P to move, O), the position
+// of index i.  Every lane of K calls it with the same arguments.  Returns the
+// number of nodes made.
+template <class R, class A, class K>
+OTHU_FN u32 search(A& tree, K& wave, u64 rootP, u64 rootO, u64 i, const Params& p) {
+    init_root(tree, wave, rootP, rootO);
+    return iterate<R>(tree, wave, playout_id0(p.game_id0, i, p.iterations, 0u), 0u, p.iterations, 1u, p.iterations, p);
+}
+
+// ---- trees that persist (include/othello_mcts_tree.h) ----
+
+// node `to_v` of `to` becomes node `from_v` of `from`, its children word included
+template <class A, class B>
+OTHU_FN void copy_node(B& to, u32 to_v, const A& from, u32 from_v) {
+    u64 P, O;
+    u32 n, s;
+    from.pos(from_v, P, O);
+    from.visits_wins(from_v, n, s);
+    to.set_pos(to_v, P, O);
+    to.set_stats(to_v, n, s, from.d(from_v));
+    to.set_link(to_v, from.link(from_v));
+}
+
+// Re-root: the subtree of `tree` below node c becomes the whole tree, c as
+// node 0, every node with its n, s, d.  The subtree is copied breadth first
+// into `half` (room for as many nodes as the tree holds), which is its own
+// queue: the nodes [head, tail) of `half` are copied but still carry their
+// children word in the OLD numbering.  A turn of the loop takes up to 64 of
+// them, gives their children blocks consecutive places from `tail` on, in queue
+// order (K's scan), copies the blocks and rewrites the words; then `half` is
+// copied back.  Every node is read and written twice: linear in the node
+// count.  A block stays contiguous and in its order, and a parent precedes its
+// children, which is all the walk asks of a numbering.  Returns the new node
+// count.  Ends in a sync.
+//   K::scan(count, f)   f(k, word, weight) for k < count <= 64; keeps word_k
+//                       and the sum of the weights below k, returns the total;
+//   K::scan_word(k), K::scan_below(k)   those, for a uniform k.
+template <class A, class B, class K>
+OTHU_FN u32 compact(A& tree, B& half, K& wave, u32 c, u32 room) {
+    wave.each(1u, [&](u32) { copy_node(half, 0u, tree, c); });
+    half.sync();
+    u32 head = 0, tail = 1;
+    while (head < tail) {
+        const u32 take = tail - head < kLanes ? tail - head : kLanes;
+        const u32 total = wave.scan(take, [&](u32 k, u32& word, u32& weight) {
+            word = half.link(head + k);
+            weight = link_cnt(word);
+        });
+        if (tail + total > room) break;  // (never in a tree this code made: `half` is not written past its end)
+        for (u32 k = 0; k < take; k++) {
+            const u32 word = wave.scan_word(k);
+            const u32 cnt = link_cnt(word), first = link_first(word), dst = tail + wave.scan_below(k);
+            if (cnt == 0) continue;
+            wave.each(cnt, [&](u32 j) { copy_node(half, dst + j, tree, first + j); });
+            wave.each(1u, [&](u32) { half.set_link(head + k, link_of(dst, cnt)); });
+        }
+        head += take;
+        tail += total;
+        half.sync();
+    }
+    wave.each(tail, [&](u32 k) { copy_node(tree, k, half, k); });
+    tree.sync();
+    return tail;
+}
+
+// whether `move` may be played at the root (P to move, O): a legal square, or
+// the pass where the mover has no move and the other side has one
+template <class R>
+OTHU_FN bool may_play(u64 P, u64 O, u32 move) {
+    const u64 legal = R::moves(P, O);
+    if (move < 64u) return (legal >> move) & 1ull;
+    return move == kPassMove && legal == 0 && R::moves(O, P) != 0;
+}
+
+// Advance the tree's root by `move` (may_play() holds).  keep and an expanded
+// root: compact() below the child the move reaches.  Otherwise the child
+// position alone.  Returns the new node count.  Ends in a sync.
+template <class R, class A, class B, class K>
+OTHU_FN u32 advance(A& tree, B& half, K& wave, u32 move, bool keep, u32 room) {
+    u64 P, O;
+    tree.pos(0u, P, O);
+    const u64 legal = R::moves(P, O);
+    const u32 link = tree.link(0u);
+    const u32 k = legal ? (u32)R::count(legal & ((1ull << (move & 63u)) - 1ull)) : 0u;
+    if (keep && link_cnt(link)) return compact(tree, half, wave, link_first(link) + k, room);
+    u64 cP, cO;
+    make_child<R>(P, O, legal, k, cP, cO);
+    tree.sync();  // (every lane has read the root)
+    init_root(tree, wave, cP, cO);
+    return 1u;
 }
 
 // The entries of a finished tree's rows at square sq: n, s, d of the root

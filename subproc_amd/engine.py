@@ -82,6 +82,12 @@ needs no eval table: every ``go`` is one ops.mcts call on the position, a Monte
 Carlo tree search of T iterations of 64 random playouts, and plays its most
 visited move.  The playouts are ``--seed``'s games; the k-th ``go`` (from 0)
 takes the ids from k * T * 64, so no two ``go``s share a playout.
+``--reuse 1`` (with ``--policy mcts``; default 0) keeps the search tree between
+moves (ops.MctsTrees): every move played, the engine's own or the opponent's,
+re-roots the tree on that move and keeps the playouts below it, and every ``go``
+runs T more iterations on what is left.  A new game, or a position the tree
+does not stand at, starts a tree from one node; the k-th such start (from 0)
+takes the ids from k * 2**40.  The tree has room for 1 + 32 T nodes.
 """
 import argparse
 import random
@@ -91,14 +97,14 @@ import numpy as np
 import torch
 
 from . import board as gboard
-from . import _lib, ops, params
+from . import _lib, codec, ops, params
 from .codec import handstr_from_coord
 
 
 class Engine:
     def __init__(self, name="GPU", policy="greedy", seed=0, weights=None, solve_empties=0, depth=1, split=0, order=0,
                  solve_task_empties=None, solve_order=None, solve_hash_bits=None, solve_wld_empties=0, nodes=None,
-                 iterations=None, explore=0.5):
+                 iterations=None, explore=0.5, reuse=0):
         top = _lib.SOLVE_MAX_EMPTIES if solve_task_empties is None else _lib.SOLVE_TREE_MAX_EMPTIES
         if not 0 <= solve_empties <= top:
             raise ValueError(f"solve_empties must lie in 0..{top}" + (
@@ -138,6 +144,14 @@ class Engine:
                 raise ValueError(f"policy mcts needs iterations in 1..{_lib.MCTS_MAX_ITERATIONS}")
         elif iterations is not None:
             raise ValueError("iterations applies to policy mcts")
+        if reuse not in (0, 1):
+            raise ValueError("reuse must be 0 or 1")
+        if reuse and policy != "mcts":
+            raise ValueError("reuse applies to policy mcts")
+        self.reuse = reuse
+        self._trees = None    # reuse: the tree (ops.MctsTrees of one), made on the first go
+        self._tree_at = None  # the position its root stands at, as _tree_key(); None: nowhere
+        self._tree_inits = 0
         self.iterations = iterations
         self.explore = float(explore)
         self.seed = seed
@@ -241,13 +255,40 @@ class Engine:
         """The Monte Carlo tree search's move for the side to move (one
         othu_mcts launch), or None when it gives none."""
         boards, side, _ = self._position()
-        r = ops.mcts(boards, side, self.iterations, explore=self.explore, seed=self.seed,
-                     game_id0=self.go_index * self.iterations * 64)
-        self.go_index += 1
+        if self.reuse:
+            if self._tree_at != self._tree_key():
+                if self._trees is None:
+                    self._trees = ops.MctsTrees(1, min(1 + 32 * self.iterations, _lib.MCTS_MAX_NODES), boards.device)
+                self._trees.init(boards, side, game_id0=self._tree_inits << 40)
+                self._tree_inits += 1
+                self._tree_at = self._tree_key()
+            r = self._trees.search(self.iterations, explore=self.explore, seed=self.seed)
+        else:
+            r = ops.mcts(boards, side, self.iterations, explore=self.explore, seed=self.seed,
+                         game_id0=self.go_index * self.iterations * 64)
+            self.go_index += 1
         sq = int(r.best_move.cpu()[0])
         if int(r.status.cpu()[0]) != _lib.MCTS_SEARCHED or sq > 63:
             return None
         return handstr_from_coord(sq & 7, sq >> 3)
+
+    def _tree_key(self):
+        return (*self.board.bitboards(), self.board.turn)
+
+    def _put(self, mv):
+        """board.put_s(mv), and with reuse the same move on the tree where it stands at the board's position."""
+        before = self._tree_key() if self.reuse else None
+        self.board.put_s(mv)
+        if self._tree_at is None or self._tree_at != before:
+            self._tree_at = None
+            return
+        try:
+            code = codec.move_code(mv)
+        except IndexError:
+            code = codec.INVALID
+        move = torch.full((1,), code, dtype=torch.uint8, device=self._trees.device)
+        ok = code != codec.INVALID and int(self._trees.advance(move, keep=True).cpu()[0]) == _lib.MCTS_TREE_READY
+        self._tree_at = self._tree_key() if ok else None
 
     def _position(self):
         """The board as a batch of one on the current device: (boards, side, empties)."""
@@ -365,11 +406,12 @@ class Engine:
         cmd = line.strip()
         if cmd == "init":
             self.board = gboard.Board()
+            self._tree_at = None
             out("init done")
         elif cmd == "go":
             mv = self.choose()
             color = "B" if self.board.turn == gboard.Black else "W"
-            self.board.put_s(mv.lower() if mv != "PS" else "PS")
+            self._put(mv.lower() if mv != "PS" else "PS")
             out("")
             out(">%s plays %s%s" % (self.name, color, mv.upper() if mv != "PS" else "PS"))
             out("")
@@ -387,7 +429,8 @@ class Engine:
         elif cmd == "verbose p":
             extra = " weights=%s" % self.weights.reshape(-1).tolist() if self.policy in ("eval", "search") else ""
             if self.policy == "mcts":
-                extra = " iterations=%d explore=%g" % (self.iterations, self.explore)
+                extra = " iterations=%d explore=%g" % (self.iterations, self.explore) + (
+                    " reuse=1" if self.reuse else "")
             if self.policy == "search":
                 extra = " depth=%d" % self.depth + (" nodes=%d" % self.nodes if self.nodes is not None else "") + (
                     " split=%d" % self.split if self.split > 0 else "") + (
@@ -425,7 +468,7 @@ class Engine:
             return False
         elif cmd:
             mv = cmd.split()[-1]
-            self.board.put_s(mv)
+            self._put(mv)
             out("")
             out("%s play %s" % (self.name, mv))
             out("")
@@ -461,7 +504,11 @@ def main(argv=None):
     p.add_argument("--iterations", type=int, default=None, metavar="T",
                    help="policy mcts: iterations of 64 random playouts per go (1..65536)")
     p.add_argument("--explore", type=float, default=0.5, metavar="C", help="policy mcts: UCT's exploration constant")
+    p.add_argument("--reuse", type=int, default=0, choices=[0, 1],
+                   help="policy mcts: 1 keeps the search tree between moves, re-rooted on every move played")
     a = p.parse_args(argv)
+    if a.policy != "mcts" and a.reuse:
+        p.error("--reuse applies to --policy mcts")
     if a.policy == "mcts" and a.iterations is None:
         p.error("--policy mcts needs --iterations")
     if a.policy != "mcts" and a.iterations is not None:
@@ -471,7 +518,7 @@ def main(argv=None):
     weights = params.read_paramgen(a.params)[1] if a.params else None
     eng = Engine(a.name, a.policy, a.seed, weights, a.solve_empties, a.depth, a.split, a.order,
                  a.solve_task_empties, a.solve_order, a.solve_hash_bits, a.solve_wld_empties, a.nodes, a.iterations,
-                 a.explore)
+                 a.explore, a.reuse)
 
     def out(s):
         sys.stdout.write(s + "\n")

@@ -146,6 +146,15 @@ class VecEnv:
         return ops.mcts(self.boards, self.turn, iterations, explore=explore, seed=seed, game_id0=game_id0,
                         max_nodes=max_nodes, log_table=log_table, want_nodes=want_nodes)
 
+    def mcts_trees(self, max_nodes, id_base=None, game_id0=0, stride=0):
+        """Search trees that persist, one per game, rooted at the current state
+        (ops.MctsTrees, initialised): `.search(T)` resumes them, `.advance(moves)`
+        re-roots them on the moves played and keeps the playouts below.  The
+        trees do not follow `step`: advance them by the same moves."""
+        trees = ops.MctsTrees(self.n, max_nodes, self.boards.device)
+        trees.init(self.boards, self.turn, id_base=id_base, game_id0=game_id0, stride=stride)
+        return trees
+
     def books(self):
         """Book text (serialize_str, board.py:214-221) of every game: oth_book_text
         on the device, one 67-byte line per game, decoded on the host."""

@@ -1044,6 +1044,289 @@ def mcts(boards, turn, iterations, explore=0.5, seed=0, game_id0=0, max_nodes=No
     return MctsResult(*rows, *root, mv, st, nd)
 
 
+MctsTreesResult = namedtuple("MctsTreesResult", MctsResult._fields + ("ran", "root_boards", "root_turn"))
+MctsPlayResult = namedtuple("MctsPlayResult", "final_boards diff plies moves hist a_black status root_visits")
+
+
+def _mcts_pair(name, x, lo, hi, cast):
+    """An argument that is one value for both players, or (A's, B's)."""
+    pair = tuple(x) if isinstance(x, (tuple, list)) else (x, x)
+    if len(pair) != 2:
+        raise ValueError(f"{name} must be one value or a pair (A's, B's)")
+    pair = tuple(cast(v) for v in pair)
+    if not all(lo <= v <= hi for v in pair):
+        raise ValueError(f"{name} must lie in {lo}..{hi}")
+    return pair
+
+
+def _mcts_nodes(max_nodes, T):
+    M = min(1 + 16 * T, _lib.MCTS_MAX_NODES) if max_nodes is None else int(max_nodes)
+    if not 1 <= M <= _lib.MCTS_MAX_NODES:
+        raise ValueError(f"max_nodes must lie in 1..{_lib.MCTS_MAX_NODES}")
+    return M
+
+
+class MctsTrees:
+    """n Monte Carlo search trees that persist on the device (othr_*,
+    include/othello_mcts_tree.h): :func:`mcts`'s trees kept between calls, so
+    that a search can be resumed and a tree re-rooted on the move that was
+    played, keeping the playouts below it.
+
+    The object owns all memory: 64 B per node and tree (the tree and the room
+    the re-rooting copies through) and 32 B of record per tree, the output
+    tensors, and the device's table of logarithms (one per device, 65,537
+    float32).  After construction every method is one asynchronous launch on
+    the current stream that allocates nothing and reads nothing on the host, so
+    it may be captured in a graph.  The tensors a method returns are the
+    object's own: the next :meth:`search` or :meth:`rows` overwrites them
+    (clone what must last).  Use one stream at a time.
+
+    ``slabs`` (uint8 (n, 64 max_nodes); the tree is the first half of a row)
+    and ``records`` (int64 (n, 4): id_base, played, nodes | turn << 32,
+    status | max_nodes << 32) are the header's layout, for tests and debugging;
+    :meth:`export` reads one tree into a canonical form."""
+
+    def __init__(self, n, max_nodes, device="cuda"):
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        self.n, self.max_nodes = n, _mcts_nodes(max_nodes, 0)
+        d = self.device = _device(device)
+        lib = _lib.load()
+        M = self.max_nodes
+        self.slabs = torch.empty((n, 2 * M * _lib.MCTS_NODE_BYTES), dtype=torch.uint8, device=d)
+        self.records = torch.zeros((n, _lib.MCTS_TREE_RECORD_BYTES // 8), dtype=torch.int64, device=d)
+        assert lib.othr_trees_slab_bytes(n, M) == max(self.slabs.numel(), 16)
+        assert lib.othr_trees_record_bytes(n) == max(self.records.numel() * 8, 16)
+        self._table = _log_table_on(_lib.MCTS_MAX_ITERATIONS, d)
+        i32 = dict(dtype=torch.int32, device=d)
+        u8 = dict(dtype=torch.uint8, device=d)
+        self._out = MctsTreesResult(torch.zeros((n, 64), **i32), torch.zeros((n, 64), **i32),
+                                    torch.zeros((n, 64), **i32), torch.zeros(n, **i32), torch.zeros(n, **i32),
+                                    torch.zeros(n, **u8), torch.zeros(n, **u8), torch.zeros(n, **i32),
+                                    torch.zeros(n, **i32), torch.zeros((n, 2), dtype=torch.int64, device=d),
+                                    torch.zeros(n, **u8))
+        self._advanced = torch.zeros(n, **u8)
+
+    def _trees(self):
+        return (self.slabs.data_ptr(), self.slabs.numel(), self.records.data_ptr(), self.records.numel() * 8, self.n,
+                _stream())
+
+    def init(self, boards, turn, id_base=None, game_id0=0, stride=0):
+        """Every tree becomes the root alone: position ``boards[i]`` with
+        ``turn[i]`` to move, no visits, ``played`` = 0.  Its playouts' ids start
+        at ``id_base[i]`` (int64 (n,) device tensor holding the uint64 bits) or
+        at ``game_id0 + i * stride``.  Overlapping boards make tree i INVALID
+        until the next init."""
+        if _n(boards) != self.n:
+            raise ValueError("boards must have n rows")
+        d = self.device
+        pb = _dev(boards, "boards", torch.int64, None, d)
+        pt = _dev(turn, "turn", torch.uint8, (self.n,), d)
+        pi = _opt(id_base, "id_base", torch.int64, (self.n,), d)
+        with torch.cuda.device(d):
+            check(_lib.load().othr_init(pb, pt, pi, int(game_id0) & (2**64 - 1), int(stride) & (2**64 - 1),
+                                        self.max_nodes, *self._trees()), "othr_init")
+
+    def search(self, iterations, explore=0.5, seed=0):
+        """``iterations`` more iterations on every tree (an int 0..65536), or
+        ``iterations[i]`` on tree i (int32 (n,) device tensor, >= 0); a tree
+        never runs more than 65,536 - n_root, and one that runs none is
+        untouched.  Iteration number ``played`` of a tree plays the games of
+        ids ``id_base + played * 64 + lane`` of ``seed``.  Returns
+        MctsTreesResult: :class:`MctsResult`'s fields (nodes always), ``ran``
+        (int32: the iterations each tree ran), ``root_boards`` (n, 2) and
+        ``root_turn``: the position the rows are about."""
+        c = float(explore)
+        if not abs(c) <= 3.0e38:
+            raise ValueError("explore must be a finite float32")
+        per = None
+        if isinstance(iterations, torch.Tensor):
+            per, T = _dev(iterations, "iterations", torch.int32, (self.n,), self.device), 0
+        else:
+            T = int(iterations)
+            if not 0 <= T <= _lib.MCTS_MAX_ITERATIONS:
+                raise ValueError(f"iterations must lie in 0..{_lib.MCTS_MAX_ITERATIONS}")
+        with torch.cuda.device(self.device):
+            check(_lib.load().othr_search(T, per, c, self._table.data_ptr(), int(seed) & (2**64 - 1), self.max_nodes,
+                                          *(t.data_ptr() for t in self._out), *self._trees()), "othr_search")
+        return self._out
+
+    def rows(self):
+        """:meth:`search`'s result with no iteration run."""
+        with torch.cuda.device(self.device):
+            check(_lib.load().othr_rows(self.max_nodes, *(t.data_ptr() for t in self._out), *self._trees()),
+                  "othr_rows")
+        return self._out
+
+    def advance(self, moves, keep=True):
+        """Play ``moves[i]`` (uint8: a square, 64 = pass, 255 = leave the tree)
+        at the root of tree i.  With ``keep`` the child the move reaches becomes
+        the root and keeps its visits and its whole subtree, the rest is
+        dropped and its room freed; otherwise (or where the root has no
+        children yet) the tree becomes the child position alone.  Returns the
+        status (uint8 (n,), the object's own tensor): _lib.MCTS_TREE_READY,
+        MCTS_TREE_INVALID, or MCTS_TREE_BADMOVE where the move is not one of
+        the root mover's (the tree is then unchanged)."""
+        pm = _dev(moves, "moves", torch.uint8, (self.n,), self.device)
+        with torch.cuda.device(self.device):
+            check(_lib.load().othr_advance(pm, int(bool(keep)), self.max_nodes, self._advanced.data_ptr(),
+                                           *self._trees()), "othr_advance")
+        return self._advanced
+
+    def export(self, i):
+        """Tree i read on the host (synchronises; for tests and debugging):
+        dict(id_base, played, nodes, turn, status, tree) with ``tree`` the
+        nodes in breadth-first order from the root, each (P, O, n, s, d, number
+        of children): a form that does not depend on how the nodes are
+        numbered in memory."""
+        M = self.max_nodes
+        rec = self.records[i].cpu().numpy().view(np.uint64)
+        out = dict(id_base=int(rec[0]), played=int(rec[1]), nodes=int(rec[2]) & 0xFFFFFFFF, turn=int(rec[2]) >> 32,
+                   status=int(rec[3]) & 0xFFFFFFFF, tree=[])
+        if out["status"] != _lib.MCTS_TREE_READY or int(rec[3]) >> 32 != M:
+            return out
+        raw = self.slabs[i, :M * _lib.MCTS_NODE_BYTES].cpu().numpy()
+        pos = raw[:16 * M].view(np.uint64).reshape(M, 2)
+        ns = raw[16 * M:24 * M].view(np.uint32).reshape(M, 2)
+        dl = raw[24 * M:].view(np.uint32).reshape(M, 2)
+        order, q = [0], 0
+        while q < len(order):
+            v = order[q]
+            q += 1
+            first, cnt = int(dl[v, 1]) & 0xFFFFF, int(dl[v, 1]) >> 20
+            out["tree"].append((int(pos[v, 0]), int(pos[v, 1]), int(ns[v, 0]), int(ns[v, 1]),
+                                int(dl[v, 0].astype(np.int32)), cnt))
+            order.extend(range(first, first + cnt))
+            if len(order) > out["nodes"]:
+                raise RuntimeError("tree %d: more nodes reachable than the record counts" % i)
+        return out
+
+
+def mcts_play(n, seed, game_id0=0, iterations=64, explore=0.5, reuse=True, a_black=None, start=None, start_turn=None,
+              record_moves=False, max_nodes=None, hist=None, device="cuda", poll=1):
+    """n whole games between two Monte Carlo tree searchers, player A and
+    player B, each with trees of its own (what two engine processes have: a
+    shared tree would hand one side's playouts to the other).  It needs no
+    evaluation function.
+
+    ``iterations`` = T or (Ta, Tb) iterations per move, ``explore`` = c or
+    (ca, cb).  Every ply is one :meth:`MctsTrees.search` over all 2 n trees --
+    the mover's T on the mover's tree, 0 on the other's (two launches where ca
+    != cb) -- the mover's ``best_move``, and one :meth:`MctsTrees.advance` of
+    both trees by it with ``keep = reuse``: with ``reuse`` both players keep
+    the subtree below every move played, their own and the opponent's; without
+    it every move is searched from a tree of one node, as a fresh :func:`mcts`
+    call would.  ``reuse`` = (A's, B's) lets one side keep and the other not
+    (then an advance per player).  A game ends where the move is 255.  The
+    playouts' ids of player p's (0: A) tree of game i start at ``id_base =
+    game_id0 + (2 i + p) * 2**32``; iteration number ``played`` of a tree
+    plays ids ``id_base + played * 64 + lane`` of ``seed``, so the games are a
+    function of the arguments alone.  (In memory A's n trees come first, then
+    B's: the trees that search at a ply then spread evenly over the grid's
+    blocks.)
+
+    ``a_black`` (uint8 (n,) device tensor; default 1, 0, 1, ...: colours
+    alternate) says where A plays Black.  ``start`` / ``start_turn`` as in
+    :func:`rollout` (default: the opening, Black to move); random opening
+    plies are the caller's business, through ``start``.  ``max_nodes`` per tree
+    defaults to 1 + 16 max(Ta, Tb).
+
+    Returns MctsPlayResult(final_boards, diff, plies, moves, hist, a_black,
+    status, root_visits): the first six as :class:`RunnerResult`, with the
+    encodings of :func:`rollout` (``moves`` 255-padded with ``record_moves``,
+    else None; ``plies`` counts passes; ``hist`` is accumulated into if given
+    and counts the finished games), so GameBooks.from_rollout takes it as it
+    is.  ``status`` is _lib.MCTS_TREE_READY, or MCTS_TREE_INVALID where the
+    start boards overlap (nothing played).  ``root_visits`` (int64) sums, over
+    a game's plies, the visits the mover's root had when it chose: with reuse
+    more than plies * T, the playouts kept.
+
+    The loop is on the host, one launch per step; the only host read is the
+    end test, once every ``poll`` plies (default every ply; a ply on finished
+    games launches but runs no iteration)."""
+    n, poll = int(n), int(poll)
+    if n < 0 or poll < 1:
+        raise ValueError("n must be >= 0 and poll >= 1")
+    Ta, Tb = _mcts_pair("iterations", iterations, 1, _lib.MCTS_MAX_ITERATIONS, int)
+    ca, cb = _mcts_pair("explore", explore, -3.0e38, 3.0e38, float)
+    keep_a, keep_b = _mcts_pair("reuse", reuse, 0, 1, lambda v: int(bool(v)))
+    M = _mcts_nodes(max_nodes, max(Ta, Tb))
+    if start is None and start_turn is not None:
+        raise ValueError("start_turn needs start")
+    d = _device(device) if start is None else start.device
+    if start is not None:
+        if _n(start) != n:
+            raise ValueError("start must have n rows")
+        _dev(start, "start", torch.int64)
+        _opt(start_turn, "start_turn", torch.uint8, (n,), start.device)
+        boards = start
+        turn = torch.ones(n, dtype=torch.uint8, device=d) if start_turn is None else start_turn.clone()
+    else:
+        boards, turn, _ = reset(n, d)
+    if a_black is None:
+        a_black = (1 - torch.arange(n, device=d) % 2).to(torch.uint8)
+    _dev(a_black, "a_black", torch.uint8, (n,), d)
+    if hist is None:
+        hist = torch.zeros(HIST_BINS, dtype=torch.int64, device=d)
+    _dev(hist, "hist", torch.int64, (HIST_BINS,), d)
+    ids = np.array([(int(game_id0) + ((2 * i + p) << 32)) & (2**64 - 1) for p in (0, 1) for i in range(n)],
+                   np.uint64).view(np.int64)
+    trees = MctsTrees(2 * n, M, d)  # tree p * n + i: player p's of game i
+    trees.init(boards.repeat(2, 1), turn.repeat(2), torch.from_numpy(ids).to(d))
+    moves = torch.full((n, MOVES_STRIDE), 255, dtype=torch.uint8, device=d) if record_moves else None
+    plies = torch.zeros(n, dtype=torch.int64, device=d)
+    root_visits = torch.zeros(n, dtype=torch.int64, device=d)
+    alive = torch.ones(n, dtype=torch.bool, device=d)
+    a_is_black = a_black != 0
+    budget = torch.zeros((2, n), dtype=torch.int32, device=d)
+    ply = 0
+    while n:
+        a_moves = (turn == BLACK) == a_is_black
+        budget[0] = torch.where(alive & a_moves, Ta, 0)
+        budget[1] = torch.where(alive & ~a_moves, Tb, 0)
+        if ca == cb:
+            r = trees.search(budget.view(-1), ca, seed)
+        else:
+            solo = budget.clone()
+            solo[1] = 0
+            trees.search(solo.view(-1), ca, seed)
+            solo[0] = 0
+            solo[1] = budget[1]
+            r = trees.search(solo.view(-1), cb, seed)
+        best, seen = r.best_move.view(2, n), r.visits.view(2, n, 64).sum(2)
+        move = torch.where(a_moves, best[0], best[1])
+        root_visits += torch.where(alive, torch.where(a_moves, seen[0], seen[1]), 0)
+        alive = alive & (move != _lib.MCTS_NO_MOVE)
+        move = torch.where(alive, move, torch.full_like(move, _lib.MCTS_NO_MOVE))
+        if moves is not None and ply < MOVES_STRIDE:
+            moves[:, ply] = move
+        plies += alive
+        if keep_a == keep_b:
+            trees.advance(move.repeat(2), keep=keep_a)
+        else:
+            hold = torch.full_like(move, _lib.MCTS_TREE_KEEP)
+            trees.advance(torch.cat((move, hold)), keep=keep_a)
+            trees.advance(torch.cat((hold, move)), keep=keep_b)
+        turn = torch.where(alive, 3 - turn, turn)
+        ply += 1
+        if ply % poll == 0 and not bool(alive.any()):
+            break
+    r = trees.rows()
+    final = r.root_boards[:n].clone()
+    status = r.status[:n].clone()
+    res = result(final)
+    done = status == _lib.MCTS_TREE_READY
+    final = torch.where(done.unsqueeze(1), final, boards)  # (a game that could not start ends where it stood)
+    diff = res.diff.to(torch.int64)
+    ones = done.to(torch.int64)
+    hist.index_add_(0, diff + 64, ones)
+    hist.index_add_(0, torch.where(diff > 0, 129, torch.where(diff < 0, 130, 131)), ones)
+    hist[HIST_BINS - 1] += (plies * ones).sum()
+    return MctsPlayResult(final, res.diff.to(torch.int8), plies.to(torch.uint8), moves, hist, a_black, status,
+                          root_visits)
+
+
 LineResult = namedtuple("LineResult", "line length value best_move status nodes end_boards end_turn")
 
 
@@ -1379,7 +1662,7 @@ __all__ = ["reset", "legal", "step", "result", "hands", "rollout", "work_word", 
            "solve_moves", "search_moves", "MovesResult",
            "solve_line", "search_line", "LineResult",
            "perft", "PerftResult",
-           "mcts", "mcts_log_table", "MctsResult",
+           "mcts", "mcts_log_table", "MctsResult", "MctsTrees", "MctsTreesResult", "mcts_play", "MctsPlayResult",
            "sample_midgame",
            "replay",
            "book_text", "features", "evaluate", "to_numpy_u64", "from_numpy_u64",

@@ -52,7 +52,7 @@ def hamlet_param_line(name, policy, weights, depth=None, solve_empties=0, nodes=
 
 def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, policy="eval", name_a="Hamlet",
                name_b="GPU", device="cuda", record=True, win_rule="reference", store=None, depth=None,
-               exact_empties=0, order=0, budget=None, solve_empties=0):
+               exact_empties=0, order=0, budget=None, solve_empties=0, iterations=None, explore=0.5, reuse=True):
     """n GameRunner games between A (``weights_a``) and B (``weights_b``,
     default params.DEFAULT_WEIGHTS), both playing ``policy``: "greedy", "eval",
     or "search" -- every policy move searched ``depth`` plies deep (an int, or
@@ -65,6 +65,13 @@ def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, po
     ``solve_empties`` = E (1..12) in place of ``exact_empties``: from E empty
     squares on the moves are the exact solver's (ops.play(solve_empties=...)),
     as the engine's --solve-empties plays them; the parameter line names it.
+    ``policy`` = "mcts": both players are Monte Carlo tree searchers of
+    ``iterations`` = T or (A's, B's) iterations per move with ``explore`` = c or
+    (A's, B's), each keeping its tree between moves where ``reuse``
+    (ops.mcts_play: a launch per step, no eval table; colours alternate, A
+    Black in game 0).  The weights and every keyword of the eval searches are
+    refused, and so are the conf's random-move budgets and colour draw: random
+    opening plies are not part of these games.
 
     Game i is global id ``game_id0 + i`` (its book id).  ``record=True``
     replays every game into books (the recorder's view); the batch stats are
@@ -77,7 +84,26 @@ def do_matches(conf, weights_a=None, n=1, seed=0, game_id0=0, weights_b=None, po
     swap = int(conf.get("proc_randomize_black_white", 0)) == 1
     wa = params.DEFAULT_WEIGHTS if weights_a is None else weights_a
     wb = params.DEFAULT_WEIGHTS if weights_b is None else weights_b
-    if policy == "search":
+    if policy != "mcts" and iterations is not None:
+        raise ValueError("iterations, explore and reuse apply to policy 'mcts' only")
+    if policy == "mcts":
+        if iterations is None:
+            raise ValueError("policy 'mcts' needs iterations=T or iterations=(Ta, Tb)")
+        if (weights_a is not None or weights_b is not None or depth is not None or exact_empties or order
+                or budget is not None or solve_empties):
+            raise ValueError("weights, depth, exact_empties, order, budget and solve_empties belong to the eval "
+                             "searches, not to policy 'mcts'")
+        if n_rand_a or n_rand_b or swap:
+            raise ValueError("policy 'mcts' plays no random plies and draws no colours: start games through "
+                             "ops.mcts_play(start=...)")
+        r = ops.mcts_play(n, seed, game_id0, iterations=iterations, explore=explore, reuse=reuse, record_moves=record,
+                          device=device)
+        (ta, tb), (ca, cb) = ops._mcts_pair("iterations", iterations, 1, 1 << 16, int), ops._mcts_pair(
+            "explore", explore, -3.0e38, 3.0e38, float)
+        tail = " reuse=1" if reuse else ""
+        line = {"a": "%s policy=mcts iterations=%d explore=%g%s" % (name_a, ta, ca, tail),
+                "b": "%s policy=mcts iterations=%d explore=%g%s" % (name_b, tb, cb, tail)}
+    elif policy == "search":
         if depth is None:
             raise ValueError("policy 'search' needs depth=D or depth=(Da, Db)")
         depth_a, depth_b = (depth, depth) if isinstance(depth, int) else depth
