@@ -23,12 +23,15 @@ import functools
 
 import numpy as np
 
+import line_ref
+import moves_ref
 import oracle
 import play_cases
 import play_ref
 import search_ref
 import solve_ref
 import tree_cases
+import window_ref
 from solve_ref import _bits, empties, mover
 
 SEED = 0x5E7C
@@ -422,3 +425,122 @@ def tie_roots(kind):
 
 
 TIE_DEPTH, TIE_TABLE = 2, "extreme"
+
+
+# ---------------------------------------------------------------- windows, per-move values and lines
+# (ops.solve(window=, wld=), ops.solve_moves / search_moves, ops.solve_line / search_line: two batches with
+# the answers of tests/window_ref.py, moves_ref.py and line_ref.py, each computed once per process)
+X_ROOTS, S_ROOTS, X_MAX_EMPTIES = 32, 16, 12
+S_SOURCES = ("uniform:20", "uniform:40", "uniform:52", "lopsided:8", "lopsided:12", "islands:6")
+S_WIDE = 8
+# (depth, table) of every search reference of batch S: the checkers take 6.1 s (line) and 2.9 s (rows) for one
+# table at depth 4, under 1 s for all of depths 1 to 3
+S_RUNS = tuple((d, table) for d in (1, 2, 3) for table in ALL_TABLES) + ((4, "default"),)
+# depth 8 at 8 empties never meets the horizon: the first X_ROOTS roots of these, which batch X holds
+FULL_DEPTH, FULL_DEPTH_CASES = 8, ("lopsided8", "islands8")
+
+
+def _readonly(d):
+    for v in d.values():
+        v.setflags(write=False)
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def batch_x():
+    """(boards, turn) of batch X: the first 32 roots of each of the twelve SOLVER cases, by name, then the rows
+    of edges() with at most 12 empties; 398 positions."""
+    eb, et, _ = edges()
+    small = empties(eb) <= X_MAX_EMPTIES
+    parts = [_source("%s:%d" % SOLVER[name][:2], X_ROOTS) for name in sorted(SOLVER)] + [(eb[small], et[small])]
+    return _freeze(np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]))
+
+
+def x_rows_of(name):
+    """Where batch X holds a SOLVER case's 32 roots, or (name, turn) an edge: a slice, or an index."""
+    if isinstance(name, tuple):
+        eb, _, _ = edges()
+        small = np.nonzero(empties(eb) <= X_MAX_EMPTIES)[0]
+        return X_ROOTS * len(SOLVER) + int(np.nonzero(small == edge(*name))[0][0])
+    k = sorted(SOLVER).index(name)
+    return slice(X_ROOTS * k, X_ROOTS * (k + 1))
+
+
+@functools.lru_cache(maxsize=None)
+def x_line():
+    """line_ref.exact of batch X."""
+    return line_ref.exact(*batch_x())
+
+
+@functools.lru_cache(maxsize=None)
+def x_roots():
+    """window_ref.roots of batch X: the exhaustive value of every root move."""
+    return window_ref.roots(*batch_x())
+
+
+@functools.lru_cache(maxsize=None)
+def x_moves():
+    """moves_ref.exact of batch X: (rows (n, 64), value, move)."""
+    return _freeze(*moves_ref.exact(x_roots()))
+
+
+@functools.lru_cache(maxsize=None)
+def x_windows():
+    """Batch X under the nine window families, built as window_ref.case_batch builds its batch: dict(boards,
+    turn, alpha, beta, value, move, family (the index into window_ref.FAMILIES), root (the row of batch X))."""
+    b, t = batch_x()
+    r = x_roots()
+    out = {k: [] for k in ("boards", "turn", "alpha", "beta", "value", "move", "family", "root")}
+    for k, name in enumerate(window_ref.FAMILIES):
+        lo, hi, keep = window_ref.family(name, r.value)
+        lo, hi = np.where(keep, lo, window_ref.LO), np.where(keep, hi, window_ref.HI)
+        v, m = window_ref.expect(r, lo, hi)
+        for key, src in zip(out, (b, t, lo, hi, v, m, np.full(r.n, k), np.arange(r.n))):
+            out[key].append(src[keep])
+    return _readonly({k: np.concatenate(v) for k, v in out.items()})
+
+
+def x_family(name):
+    """The rows of x_windows() of one family."""
+    return np.nonzero(x_windows()["family"] == window_ref.FAMILIES.index(name))[0]
+
+
+@functools.lru_cache(maxsize=None)
+def batch_s():
+    """(boards, turn) of batch S: the first 16 roots of each of S_SOURCES, wide(8), every row of edges(); 124
+    positions."""
+    eb, et, _ = edges()
+    parts = [_source(src, S_ROOTS) for src in S_SOURCES] + [wide(S_WIDE), (eb, et)]
+    return _freeze(np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]))
+
+
+def s_row_of(name, turn):
+    """The row of batch S that holds an edge."""
+    return S_ROOTS * len(S_SOURCES) + S_WIDE + edge(name, turn)
+
+
+@functools.lru_cache(maxsize=None)
+def s_line(depth, table):
+    """line_ref.search of batch S."""
+    return line_ref.search(*batch_s(), depth, TABLES[table])
+
+
+@functools.lru_cache(maxsize=None)
+def s_moves(depth, table):
+    """moves_ref.search of batch S: (rows (n, 64), value, move)."""
+    return _freeze(*moves_ref.search(*batch_s(), depth, TABLES[table]))
+
+
+def exact_rows_times_t(rows, value, move):
+    """What the search rows are where the horizon is never met: T times the exact rows."""
+    return np.where(rows == moves_ref.NOT_A_MOVE, moves_ref.NOT_A_MOVE32, rows * T), value * T, move
+
+
+@functools.lru_cache(maxsize=None)
+def full_depth_case(name):
+    """(boards, turn, exact line, exact (rows, value, move)) of a FULL_DEPTH_CASES entry, taken from batch X: at
+    depth 8 the search line is that line with the value times T, the search rows exact_rows_times_t of those."""
+    sel = x_rows_of(name)
+    b, t = batch_x()
+    assert (empties(b[sel]) <= FULL_DEPTH).all()
+    return b[sel], t[sel], {k: v[sel] for k, v in x_line().items()}, tuple(v[sel] for v in x_moves())

@@ -1,10 +1,13 @@
 """tests/synthetic_cases.py's claims about its own positions, checked with the C
-oracle and the exhaustive checkers alone, and the five host drivers of the
-searches' cores (tools/diag/{solve,search,tree,solve_tree,play}_host.cpp: plain
-C++ rules, plain loads and stores) against the checkers on every family: a rules
-bug in a *_core.hpp shows here, before any GPU run.  The two tree drivers run
-every position's tasks in four orders (forward, reverse, shuffled, nothing
-shared); every driver runs with order 0 and 1.  CPU only."""
+oracle and the exhaustive checkers alone, and the eight host drivers of the
+searches' cores (tools/diag/{solve,search,tree,solve_tree,play,solve_window,
+moves,line}_host.cpp: plain C++ rules, plain loads and stores) against the
+checkers on every family: a rules bug in a *_core.hpp shows here, before any GPU
+run.  The two tree drivers run every position's tasks in four orders (forward,
+reverse, shuffled, nothing shared); every driver runs with order 0 and 1.  The
+last three drivers (root windows, the value of every root move, the principal
+variation) run on batches X and S, with the helpers of their own host files.
+CPU only."""
 import os
 import shutil
 import subprocess
@@ -15,10 +18,16 @@ import pytest
 import oracle
 import play_ref
 import search_ref
+import line_ref
+import moves_ref
 import solve_cases
 import solve_ref
 import synthetic_cases as sc
+import test_line_host as line_host
+import test_moves_host as moves_host
+import test_solve_window_host as window_host
 import tree_cases
+import window_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVERS = ("solve", "search", "tree", "solve_tree", "play")
@@ -398,3 +407,223 @@ def test_ties_in_the_host_builds(host, tmp_path, order):
     b, t, rv, rm = sc.tie_roots("search")
     same(search_host(host, tmp_path, b, t, sc.TIE_DEPTH, sc.TIE_TABLE, order), (rv, rm), "search")
     same_in_all_orders(tree_host(host, tmp_path, b, t, sc.TIE_DEPTH, 1, sc.TIE_TABLE, order), (rv, rm), "tree")
+
+
+# ---------------------------------------------------------------- windows, per-move values and lines: batches X and S
+def test_what_batches_x_and_s_hold():
+    """From the oracle and the checkers alone: a drift in the generators shows here."""
+    b, t = sc.batch_x()
+    emp = solve_ref.empties(b)
+    own = sc.popcount(oracle.legal(b, t))
+    forced, over = sc.root_kinds(b, t)
+    assert len(t) == 398 and emp.max() == 8 and not b.flags.writeable
+    assert (forced.sum(), over.sum()) == (21, 23)
+    ln = sc.x_line()
+    assert ((ln["line"] == 64).any(1).sum(), (ln["line"][:, 1:] == 64).any(1).sum()) == (139, 128)
+    assert (solve_ref.empties(ln["end_boards"]) > 0).sum() == 51 and ln["length"].max() == 13
+    assert ((own == emp) & (emp > 0)).sum() == 86 and own.max() == 8  # the last of max(max_empties, 1) task slots
+    r, w = sc.x_roots(), sc.x_windows()
+    assert len(w["turn"]) == 3582 == 9 * len(t) and set(w["family"].tolist()) == set(range(9))
+    wld = sc.x_family("wld")
+    assert ((w["value"][wld] == 1).sum(), (w["value"][wld] == -1).sum()) == (203, 177)
+    assert ((r.value >= 1).sum(), (r.value <= -1).sum()) == (203, 177)
+    assert (w["move"][sc.x_family("on_beta")] < 64).sum() == 354
+    assert np.abs(r.value).max() == 64 and (np.abs(r.value) >= 61).sum() >= 8  # the ends of the windows' range
+    rows, value, move = sc.x_moves()
+    assert (value == r.value).all() and (value == ln["value"]).all() and (move == ln["best_move"]).all()
+    b, t = sc.batch_s()
+    forced, over = sc.root_kinds(b, t)
+    assert len(t) == 124 and (forced.sum(), over.sum()) == (6, 22)
+    assert sc.popcount(oracle.legal(b, t)).max() == 34
+    ln = sc.s_line(4, "default")
+    assert ((ln["line"] == 64).any(1).sum(), (ln["length"] < 4).sum()) == (17, 32)
+    for depth, table in sc.S_RUNS:  # the two checkers agree with each other
+        rows, value, move = sc.s_moves(depth, table)
+        assert (value == sc.s_line(depth, table)["value"]).all(), (depth, table)
+        assert (move == sc.s_line(depth, table)["best_move"]).all(), (depth, table)
+    for name in sc.FULL_DEPTH_CASES:
+        fb, ft, _, _ = sc.full_depth_case(name)
+        assert len(ft) == 32 and (fb == sc.solver_inputs(name)[0][:32]).all()
+
+
+def test_the_checkers_rows_move_with_the_squares():
+    """What the GPU file's image tests of the rows rely on: an image's row, taken back through its permutation,
+    is its root's; exact rows at 6 empties, search rows at depth 2 on the three tables."""
+    for family in ("uniform", "lopsided"):
+        b, t = sc.FAMILIES[family](6)
+        ib, it, perm = sc.images(b[:8], t[:8])
+        rows = np.take_along_axis(moves_ref.exact(window_ref.roots(ib, it))[0], perm, 1).reshape(8, 16, 64)
+        assert (rows == rows[:, :1]).all() and (rows != moves_ref.NOT_A_MOVE).any()
+    b, t = sc.uniform(30)
+    ib, it, perm = sc.images(b[:4], t[:4])
+    for table in sc.ALL_TABLES:
+        rows = np.take_along_axis(moves_ref.search(ib, it, 2, sc.TABLES[table])[0], perm, 1).reshape(4, 16, 64)
+        assert (rows == rows[:, :1]).all()
+
+
+@pytest.fixture(scope="module")
+def window_exe(tmp_path_factory):
+    return window_host.compiled(tmp_path_factory, "solve_window_host", ["-O2", "-fopenmp"])
+
+
+@pytest.fixture(scope="module")
+def moves_exe(tmp_path_factory):
+    return moves_host.compiled(tmp_path_factory, "moves_host", ["-O2", "-fopenmp"])
+
+
+@pytest.fixture(scope="module")
+def line_exe(tmp_path_factory):
+    return line_host.compiled(tmp_path_factory, "line_host", ["-O2", "-fopenmp"])
+
+
+def run_windows(exe, tmp_path, rows, task_empties, npp, threads, what):
+    w = sc.x_windows()
+    got = window_host.run(exe, tmp_path, ("a", 16, task_empties, npp, threads), w["boards"][rows], w["turn"][rows],
+                          w["alpha"][rows], w["beta"][rows])
+    window_host.check_mode_a(got, w["value"][rows], w["move"][rows], what)
+    return got
+
+
+@pytest.mark.parametrize("npp", [64, 4096])
+@pytest.mark.parametrize("task_empties", [1, 3])
+def test_window_host_on_batch_x_in_every_family(window_exe, tmp_path, task_empties, npp):
+    w = sc.x_windows()
+    got = run_windows(window_exe, tmp_path, slice(None), task_empties, npp, THREADS, (task_empties, npp))
+    full = w["family"] == 0
+    assert (got[:, 3] <= got[:, 4]).all() and (got[full, 3] == got[full, 4]).all()  # a subtree of the full window's
+    over = sc.root_kinds(w["boards"], w["turn"])[1]
+    assert (got[over, 1] == 255).all() and (got[over, 3] == 0).all()
+
+
+def check_exact_rows(got, want, b, t, what):
+    moves_host.check(got, want, SOLVED, what)
+    forced, over = sc.root_kinds(b, t)
+    assert (got[3][over] == 0).all() and (got[1][over] == 255).all() and (got[1][forced] == 64).all(), what
+    assert (got[4][forced | over] == moves_ref.NOT_A_MOVE).all(), what
+
+
+@pytest.mark.parametrize("level", [8, 12])
+def test_moves_host_exact_rows_on_batch_x(moves_exe, tmp_path, level):
+    """Level 8: the roots of 8 empties with 8 moves fill the last of their task slots."""
+    b, t = sc.batch_x()
+    check_exact_rows(moves_host.run(moves_exe, tmp_path, "solve", b, t, level), sc.x_moves(), b, t, level)
+
+
+def check_search_rows(exe, tmp_path, runs):
+    b, t = sc.batch_s()
+    _, over = sc.root_kinds(b, t)
+    for depth, table in runs:
+        got = moves_host.run(exe, tmp_path, "search", b, t, depth, sc.TABLES[table])
+        moves_host.check(got, sc.s_moves(depth, table), SEARCHED, (depth, table))
+        assert (got[3][over] == 0).all() and (got[4][over] == moves_ref.NOT_A_MOVE32).all(), (depth, table)
+
+
+@pytest.mark.parametrize("depth,table", sc.S_RUNS)
+def test_moves_host_search_rows_on_batch_s(moves_exe, tmp_path, depth, table):
+    check_search_rows(moves_exe, tmp_path, [(depth, table)])
+
+
+def check_exact_lines(exe, tmp_path):
+    b, t = sc.batch_x()
+    got = line_host.run_solve(exe, tmp_path, b, t)
+    assert (got["status"] == SOLVED).all()
+    line_host.same_line(got, sc.x_line(), "batch X")
+    assert (line_ref.end_score(got["end_boards"], t) == got["value"]).all()
+    forced, over = sc.root_kinds(b, t)
+    assert (got["line"][forced, 0] == 64).all() and (got["length"][over] == 0).all()
+    assert (got["best_move"][over] == 255).all() and (got["nodes"][over] == 0).all()
+
+
+def check_search_lines(exe, tmp_path, runs):
+    b, t = sc.batch_s()
+    for depth, table in runs:
+        for order in (0, 1):
+            got = line_host.run_search(exe, tmp_path, b, t, depth, sc.TABLES[table], order)
+            assert (got["status"] == SEARCHED).all()
+            line_host.same_line(got, sc.s_line(depth, table), (depth, table, order))
+            assert (line_ref.end_score(got["end_boards"], t, sc.TABLES[table]) == got["value"]).all()
+
+
+def test_line_host_exact_lines_on_batch_x(line_exe, tmp_path):
+    check_exact_lines(line_exe, tmp_path)
+
+
+@pytest.mark.parametrize("depth,table", sc.S_RUNS)
+def test_line_host_search_lines_on_batch_s(line_exe, tmp_path, depth, table):
+    check_search_lines(line_exe, tmp_path, [(depth, table)])
+
+
+@pytest.mark.parametrize("name", sc.FULL_DEPTH_CASES)
+def test_the_three_drivers_at_full_depth(window_exe, moves_exe, line_exe, tmp_path, name):
+    """Depth 8 at 8 empties: the search rows and the search line are the exact ones times T on every table; the
+    window driver on the same roots with tasks of six empties, which no other run here has."""
+    b, t, line, exact = sc.full_depth_case(name)
+    sel = sc.x_rows_of(name)
+    pairs = np.nonzero((sc.x_windows()["root"] >= sel.start) & (sc.x_windows()["root"] < sel.stop))[0]
+    assert len(pairs) == 9 * 32
+    run_windows(window_exe, tmp_path, pairs, 6, 64, THREADS, name)
+    for table in sc.ALL_TABLES:
+        w = sc.TABLES[table]
+        got = moves_host.run(moves_exe, tmp_path, "search", b, t, sc.FULL_DEPTH, w)
+        moves_host.check(got, sc.exact_rows_times_t(*exact), SEARCHED, (name, table))
+        for order in (0, 1):
+            got = line_host.run_search(line_exe, tmp_path, b, t, sc.FULL_DEPTH, w, order)
+            assert (got["status"] == SEARCHED).all()
+            line_host.same_line(got, line, (name, table, order), scale=T)
+            assert (line_ref.end_score(got["end_boards"], t, w) == got["value"]).all()
+
+
+def test_line_host_depths_per_position_on_batch_s(line_exe, tmp_path):
+    """0 is not searched, 9 is out of range, 8 only where it ends the game (at most 8 empties; depth 3 on the
+    other rows of that index): test_line_host.deep_and_mixed_checks' statuses."""
+    b, t = sc.batch_s()
+    depths = per_position_depths(b)
+    w = sc.TABLES["default"]
+    got = line_host.run_search(line_exe, tmp_path, b, t, depths, w, 1)
+    check_per_position(got, b, t, depths, w)
+
+
+def per_position_depths(boards):
+    d = np.array([(0, 1, 2, 3, 8, 9)[i % 6] for i in range(len(boards))])
+    return np.where((d == 8) & (solve_ref.empties(boards) > 8), 3, d)
+
+
+def check_per_position(got, b, t, depths, weights):
+    """A per-position result of batch S on the "default" table against the references of each depth."""
+    assert (got["status"] == np.where(depths == 0, line_host.LIMIT,
+                                      np.where(depths == 9, line_host.BADDEPTH, SEARCHED))).all()
+    off = (depths == 0) | (depths == 9)
+    assert (got["length"][off] == 0).all() and (got["value"][off] == 0).all() and (got["nodes"][off] == 0).all()
+    assert (got["best_move"][off] == 255).all() and (got["line"][off] == 255).all()
+    assert (got["end_boards"][off] == b[off]).all()
+    for depth in (1, 2, 3, 8):
+        sel = depths == depth
+        assert sel.sum() >= 4  # (7 rows of batch S at depth 8, 20 or more at the others)
+        ref = line_ref.search(b[sel], t[sel], 8, weights) if depth == 8 else \
+            {k: v[sel] for k, v in sc.s_line(depth, "default").items()}
+        line_host.same_line({k: v[sel] for k, v in got.items()}, ref, ("per position", depth))
+    assert (line_ref.end_score(got["end_boards"][~off], t[~off], weights) == got["value"][~off]).all()
+
+
+SANITIZED = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+S_DEFAULT_RUNS = [(d, "default") for d in (1, 2, 3)]
+
+
+def test_window_host_under_the_address_and_undefined_behaviour_sanitizers(tmp_path_factory, tmp_path):
+    exe = window_host.compiled(tmp_path_factory, "solve_window_host_asan", SANITIZED)
+    run_windows(exe, tmp_path, slice(None), 3, 4096, 1, "asan")
+    run_windows(exe, tmp_path, slice(None), 1, 64, 1, "asan, 64 nodes")
+
+
+def test_moves_host_under_the_address_and_undefined_behaviour_sanitizers(tmp_path_factory, tmp_path):
+    exe = moves_host.compiled(tmp_path_factory, "moves_host_asan", SANITIZED)
+    b, t = sc.batch_x()
+    for level in (8, 12):
+        check_exact_rows(moves_host.run(exe, tmp_path, "solve", b, t, level), sc.x_moves(), b, t, ("asan", level))
+    check_search_rows(exe, tmp_path, S_DEFAULT_RUNS)
+
+
+def test_line_host_under_the_address_and_undefined_behaviour_sanitizers(tmp_path_factory, tmp_path):
+    exe = line_host.compiled(tmp_path_factory, "line_host_asan", SANITIZED)
+    check_exact_lines(exe, tmp_path)
+    check_search_lines(exe, tmp_path, S_DEFAULT_RUNS)
