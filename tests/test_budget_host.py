@@ -10,48 +10,35 @@ tests/synthetic_cases.py, with an overlapping board; both orders, budgets 1, 8,
 64, 512, 4096 and caps 1, 4, 8.  The same under
 -fsanitize=address,undefined, as a process of its own.  CPU only."""
 import functools
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import budget_ref
+import host_programs as hp
 import play_ref
 import search_ref
 import synthetic_cases
 import tree_cases
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIAG = os.path.join(ROOT, "tools", "diag")
 BUDGETS = (1, 8, 64, 512, 4096)
 CAPS = (1, 4, 8)
 BMAX = max(BUDGETS)
-SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-
-
-def compiled(tmp_path_factory, source, name, flags):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.check_call(["g++", "-std=c++17", *flags, "-o", exe, os.path.join(DIAG, source)])
-    return exe
 
 
 @pytest.fixture(scope="module")
 def binary(tmp_path_factory):
-    return compiled(tmp_path_factory, "budget_host.cpp", "budget_host", ["-O2", "-fopenmp"])
+    return hp.compiled(tmp_path_factory, "budget_host")
 
 
 @pytest.fixture(scope="module")
 def binary_asan(tmp_path_factory):
-    return compiled(tmp_path_factory, "budget_host.cpp", "budget_host_asan", SAN)
+    return hp.compiled(tmp_path_factory, "budget_host", hp.SANITIZED)
 
 
 @pytest.fixture(scope="module")
 def fixed(tmp_path_factory):
-    return compiled(tmp_path_factory, "search_host.cpp", "search_host", ["-O2", "-fopenmp"])
+    return hp.compiled(tmp_path_factory, "search_host")
 
 
 @functools.lru_cache(maxsize=None)
@@ -71,40 +58,27 @@ def inputs():
     return b, t
 
 
-def write_positions(path, boards, turn, budgets=None):
-    with open(path, "w") as f:
-        for i, ((b, w), t) in enumerate(zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist())):
-            f.write("%x %x %d" % (b, w, t) + ("\n" if budgets is None else " %d\n" % int(budgets[i])))
-
-
-def write_weights(path, weights):
-    with open(path, "w") as f:
-        f.write(" ".join(str(int(x)) for x in np.asarray(weights).reshape(-1)))
-
-
 def run_budget(exe, tmp, boards, turn, budgets, cap, weights, order):
     inp, out, wf = str(tmp / "bin"), str(tmp / "bout"), str(tmp / "bw")
     budgets = np.broadcast_to(np.asarray(budgets, np.int64), (len(turn),))
-    write_positions(inp, boards, turn, budgets)
-    write_weights(wf, weights)
-    r = subprocess.run([exe, "search", inp, out, wf, str(cap), str(order), "8"], capture_output=True, text=True)
-    assert r.returncode == 0 and "Sanitizer" not in r.stderr, r.stderr[-2000:]
-    a = np.array([[int(x) for x in ln.split()] for ln in open(out)], np.int64).reshape(len(turn), 5)
+    hp.write_positions(inp, boards, turn, budgets)
+    hp.write_weights(wf, weights)
+    hp.run([exe, "search", inp, out, wf, cap, order, 8])
+    a = hp.read_rows(out, (len(turn), 5))
     return dict(value=a[:, 0], best_move=a[:, 1], status=a[:, 2], depth=a[:, 3], nodes=a[:, 4])
 
 
 def fixed_depth(exe, tmp, boards, turn, weights, order, limit):
     """search_at(d) of the existing host build, each depth run once."""
     inp, wf = str(tmp / "fin"), str(tmp / "fw")
-    write_positions(inp, boards, turn)
-    write_weights(wf, weights)
+    hp.write_positions(inp, boards, turn)
+    hp.write_weights(wf, weights)
 
     @functools.lru_cache(maxsize=None)
     def search_at(d):
         out = str(tmp / ("fout%d" % d))
-        r = subprocess.run([exe, inp, out, wf, str(d), str(limit), "8", str(order)], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-2000:]
-        a = np.array([[int(x) for x in ln.split()] for ln in open(out)], np.int64).reshape(len(turn), 4)
+        hp.run([exe, inp, out, wf, d, limit, 8, order])
+        a = hp.read_rows(out, (len(turn), 4))
         return a[:, 0], a[:, 1], a[:, 2], a[:, 3]
 
     return search_at
@@ -163,29 +137,11 @@ def test_value_and_move_are_the_exhaustive_checkers_at_the_depth_reached(binary,
         assert checked >= len(t) // 2
 
 
-def game_args(path, n, seed, depths, budgets, exact, n_rand, swap, limit, start, start_turn, wa, wb):
-    with open(path, "w") as f:
-        f.write("%d %d 0 %d %d %d %d %d %d %d %d %d %d\n" % (n, seed, depths[0], depths[1], budgets[0], budgets[1],
-                                                             exact, n_rand[0], n_rand[1], int(swap), limit,
-                                                             int(start is not None)))
-        for w in (wa, wb):
-            f.write(" ".join(str(int(x)) for x in np.asarray(w).reshape(-1)) + "\n")
-        if start is not None:
-            for (bl, wh), t in zip(np.asarray(start, np.uint64).tolist(), np.asarray(start_turn).tolist()):
-                f.write("%x %x %d\n" % (bl, wh, t))
-
-
 def run_games(exe, tmp, order, **kw):
     args, out = str(tmp / "gargs"), str(tmp / "gout")
-    game_args(args, **kw)
-    r = subprocess.run([exe, "play", args, out, str(order), "8"], capture_output=True, text=True)
-    assert r.returncode == 0 and "Sanitizer" not in r.stderr, r.stderr[-2000:]
-    rows = [ln.split() for ln in open(out)]
-    return dict(a_black=np.array([int(r[0]) for r in rows]),
-                final_boards=np.array([[int(r[1], 16), int(r[2], 16)] for r in rows], np.uint64),
-                diff=np.array([int(r[3]) for r in rows]), plies=np.array([int(r[4]) for r in rows]),
-                status=np.array([int(r[5]) for r in rows]), nodes=np.array([int(r[6]) for r in rows]),
-                moves=np.array([list(bytes.fromhex(r[7])) for r in rows], np.uint8))
+    hp.write_game_args(args, **kw)
+    hp.run([exe, "play", args, out, order, 8])
+    return hp.read_games(out)
 
 
 def budget_chooser(fixed, tmp, tables, caps, budgets, exact, order):

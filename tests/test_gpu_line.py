@@ -4,14 +4,11 @@ behind a value from the exact solver and from the depth-limited search, its
 agreement with ops.solve / ops.search, deep lines against the existing calls,
 the node limit, depths per position, the launch plumbing, and what is built on
 them (the VecEnv methods, the engine's `pv`).  All comparisons are exact."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
+import host_programs as hp
 import line_ref
 import oracle
 import solve_cases
@@ -25,7 +22,6 @@ from subproc_amd import _lib, ops  # noqa: E402
 from subproc_amd.engine import Engine  # noqa: E402
 from subproc_amd.env import VecEnv  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOLVED, SKIPPED, INVALID, LIMIT = _lib.SOLVE_SOLVED, _lib.SOLVE_SKIPPED, _lib.SOLVE_INVALID, _lib.SOLVE_LIMIT
 BADDEPTH = _lib.LINE_BADDEPTH
 T = line_ref.T
@@ -349,12 +345,8 @@ def test_results_do_not_depend_on_the_batch_or_the_grid(monkeypatch):
     assert ops.work_word("cuda").item() == 0
 
 
-def test_node_counts_are_the_host_programs(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "line_host")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fopenmp", "-o", exe,
-                           os.path.join(ROOT, "tools", "diag", "line_host.cpp")])
+def test_node_counts_are_the_host_programs(tmp_path_factory, tmp_path):
+    exe = hp.compiled(tmp_path_factory, "line_host")
     b, t, _, _ = exact_batch()
     got = gpu_solve_line(b, t, max_empties=9)
     h = run_solve(exe, tmp_path, b, t, max_empties=9)

@@ -5,18 +5,18 @@ ops.solve / ops.search, the node limit per move, the launch plumbing, and what
 is built on them (GameBooks.endgame_losses, the engine's `hint`).  All
 comparisons are exact."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_programs as hp
 import moves_ref
 import oracle
 import solve_cases
 import solve_ref
 import tree_cases
+from test_moves_host import run as moves_host_run
 
 pytestmark = pytest.mark.gpu
 
@@ -224,25 +224,12 @@ def test_depth_1_rows_are_the_childrens_evals_from_the_root_movers_side(table):
 
 
 # ---------------------------------------------------------------- the host program's node counts
-def test_one_lane_node_counts_are_the_host_programs(tmp_path):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path / "moves_host")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fopenmp", "-o", exe,
-                           os.path.join(ROOT, "tools", "diag", "moves_host.cpp")])
+def test_one_lane_node_counts_are_the_host_programs(tmp_path_factory, tmp_path):
+    exe = hp.compiled(tmp_path_factory, "moves_host")
 
     def host(mode, b, t, level, weights=None):
-        inp, out, wf = str(tmp_path / "in"), str(tmp_path / "out"), str(tmp_path / "w")
-        with open(inp, "w") as f:
-            for (x, y), s in zip(np.asarray(b, np.uint64).tolist(), np.asarray(t).tolist()):
-                f.write("%x %x %d\n" % (x, y, s))
-        args = [exe, mode, inp, out]
-        if weights is not None:
-            with open(wf, "w") as f:
-                f.write(" ".join(str(int(x)) for x in np.asarray(weights).reshape(-1)))
-            args.append(wf)
-        subprocess.check_call(args + [str(level), "0", "8"])
-        return np.array([[int(x) for x in ln.split()] for ln in open(out)], np.int64).reshape(len(t), 68)
+        value, move, status, nodes, rows = moves_host_run(exe, tmp_path, mode, b, t, level, weights)
+        return np.column_stack([value, move, status, nodes, rows])
 
     b, t, want, _, _ = exact_batch()
     got = gpu_solve_moves(b, t, max_empties=9)

@@ -8,46 +8,26 @@ special3 at depths 1..4, both tables, both orders; depth 8 at 6 empties, where
 the line must be the exact line; a per-position depth array holding 0, 1, 8 and
 9.  The same under -fsanitize=address,undefined, as a process of its own.
 CPU only."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_programs as hp
 import line_ref
 import solve_cases
 import tree_cases
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIAG = os.path.join(ROOT, "tools", "diag")
-SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 SOLVED, INVALID, LIMIT, BADDEPTH = 1, 2, 3, 6
 FIELDS = ("value", "best_move", "status", "nodes", "length", "end_boards", "end_turn", "line")
 
 
-def compiled(tmp_path_factory, name, flags):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.check_call(["g++", "-std=c++17", *flags, "-o", exe, os.path.join(DIAG, "line_host.cpp")])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def binary(tmp_path_factory):
-    return compiled(tmp_path_factory, "line_host", ["-O2", "-fopenmp"])
+    return hp.compiled(tmp_path_factory, "line_host")
 
 
 @pytest.fixture(scope="module")
 def binary_asan(tmp_path_factory):
-    return compiled(tmp_path_factory, "line_host_asan", SAN)
-
-
-def write_positions(path, boards, turn, depths=None):
-    with open(path, "w") as f:
-        for i, ((b, w), t) in enumerate(zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist())):
-            f.write("%x %x %d" % (b, w, t) + ("\n" if depths is None else " %d\n" % int(depths[i])))
+    return hp.compiled(tmp_path_factory, "line_host", hp.SANITIZED)
 
 
 def read_lines(path, n):
@@ -63,9 +43,8 @@ def read_lines(path, n):
 
 def run_solve(exe, tmp, boards, turn, max_empties=12, limit=0):
     inp, out = str(tmp / "lin"), str(tmp / "lout")
-    write_positions(inp, boards, turn)
-    r = subprocess.run([exe, "solve", inp, out, str(max_empties), str(limit), "8"], capture_output=True, text=True)
-    assert r.returncode == 0 and "Sanitizer" not in r.stderr, r.stderr[-2000:]
+    hp.write_positions(inp, boards, turn)
+    hp.run([exe, "solve", inp, out, max_empties, limit, 8])
     return read_lines(out, len(turn))
 
 
@@ -73,12 +52,9 @@ def run_search(exe, tmp, boards, turn, depth, weights, order=0, limit=0):
     """depth: an int, or an array of n (the per-position form)."""
     inp, out, wf = str(tmp / "lin"), str(tmp / "lout"), str(tmp / "lw")
     per = not np.isscalar(depth)
-    write_positions(inp, boards, turn, depth if per else None)
-    with open(wf, "w") as f:
-        f.write(" ".join(str(int(x)) for x in np.asarray(weights).reshape(-1)))
-    r = subprocess.run([exe, "search", inp, out, wf, "-1" if per else str(depth), str(order), str(limit), "8"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and "Sanitizer" not in r.stderr, r.stderr[-2000:]
+    hp.write_positions(inp, boards, turn, depth if per else None)
+    hp.write_weights(wf, weights)
+    hp.run([exe, "search", inp, out, wf, -1 if per else depth, order, limit, 8])
     return read_lines(out, len(turn))
 
 

@@ -3,39 +3,23 @@ mcts_core.hpp's walk in plain C++ with a plain random playout) against
 tests/mcts_ref.py's checker over the oracle, field for field on every set of
 tests/mcts_cases.py; and the same under -fsanitize=address,undefined, as a
 process of its own.  DESIGN.md §28.  CPU only."""
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_programs as hp
 import mcts_cases
 import mcts_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIAG = os.path.join(ROOT, "tools", "diag")
-SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-
-
-def compiled(tmp_path_factory, name, flags):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off", *flags, "-o", exe,
-                           os.path.join(DIAG, "mcts_host.cpp")])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def binary(tmp_path_factory):
-    return compiled(tmp_path_factory, "mcts_host", ["-O2", "-fopenmp"])
+    return hp.compiled(tmp_path_factory, "mcts_host")
 
 
 @pytest.fixture(scope="module")
 def binary_asan(tmp_path_factory):
-    return compiled(tmp_path_factory, "mcts_host_asan", SAN)
+    return hp.compiled(tmp_path_factory, "mcts_host", hp.SANITIZED)
 
 
 def bits(x):
@@ -45,18 +29,14 @@ def bits(x):
 def run(exe, tmp, boards, turn, T, c, M, seed=mcts_cases.SEED, game_id0=mcts_cases.GAME_ID0, table=None):
     inp, out = str(tmp / "min"), str(tmp / "mout")
     table = mcts_ref.log_table(T) if table is None else table
-    with open(inp, "w") as f:
-        for (b, w), t in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist()):
-            f.write("%x %x %d\n" % (b, w, t))
+    hp.write_positions(inp, boards, turn)
+    with open(inp, "a") as f:
         for x in table:
             f.write("L %x\n" % bits(x))
-    r = subprocess.run([exe, inp, out, str(T), "%x" % bits(c), str(seed), str(game_id0), str(M), "8"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and "Sanitizer" not in r.stderr, r.stderr[-2000:]
-    lines = open(out).read().splitlines()
-    a = np.array([[int(x) for x in ln.split()] for ln in lines[:-1]], np.int64).reshape(len(turn), 5 + 192)
+    hp.run([exe, inp, out, T, "%x" % bits(c), seed, game_id0, M, 8])
+    a, last = hp.read_rows(out, (len(turn), 5 + 192), trailer=True)
     return dict(status=a[:, 0], best_move=a[:, 1], nodes=a[:, 2], root_wins=a[:, 3], root_diffs=a[:, 4],
-                visits=a[:, 5:69], wins=a[:, 69:133], diffs=a[:, 133:197], plies=int(lines[-1].split()[1]))
+                visits=a[:, 5:69], wins=a[:, 69:133], diffs=a[:, 133:197], plies=int(last[1]))
 
 
 @pytest.mark.parametrize("name", ["small", "explore", "long"])

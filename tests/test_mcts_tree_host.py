@@ -7,42 +7,28 @@ tests/mcts_cases.py's `small` with M at its default and with M = 24 (trees that
 are full before the re-root and have room after it); and the same under
 -fsanitize=address,undefined, as a process of its own.  DESIGN.md §29.  CPU
 only."""
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_programs as hp
 import mcts_cases
 import mcts_ref
 import mcts_tree_cases as cases
 import mcts_tree_ref as ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIAG = os.path.join(ROOT, "tools", "diag")
-SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 MS = (mcts_ref.default_nodes(40), 24)
-
-
-def compiled(tmp_path_factory, name, flags):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off", *flags, "-o", exe,
-                           os.path.join(DIAG, "mcts_tree_host.cpp")])
-    return exe
 
 
 @pytest.fixture(scope="module")
 def binary(tmp_path_factory):
-    return compiled(tmp_path_factory, "mcts_tree_host", ["-O2"])
+    return hp.compiled(tmp_path_factory, "mcts_tree_host")
 
 
 @pytest.fixture(scope="module")
 def binary_asan(tmp_path_factory):
-    return compiled(tmp_path_factory, "mcts_tree_host_asan", SAN)
+    return hp.compiled(tmp_path_factory, "mcts_tree_host", hp.SANITIZED)
 
 
 def bits(x):
@@ -57,15 +43,13 @@ def run(exe, tmp, boards, turn, ids, script, M, c=cases.C, seed=cases.SEED, tabl
     """The program's answers, one entry per operation that prints: ("R", fields), ("A", status, moves) or
     ("T", nodes, played, canonical trees)."""
     inp, scr, out = str(tmp / "tin"), str(tmp / "tscript"), str(tmp / "tout")
-    with open(inp, "w") as f:
-        for (b, w), t, i in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist(), ids):
-            f.write("%x %x %d %d\n" % (b, w, t, i))
+    hp.write_positions(inp, boards, turn, ids)
+    with open(inp, "a") as f:
         for x in cases.TABLE[:table_last + 1]:
             f.write("L %x\n" % bits(x))
     with open(scr, "w") as f:
         f.write("\n".join(script) + "\n")
-    r = subprocess.run([exe, inp, scr, out, "%x" % bits(c), str(seed), str(M)], capture_output=True, text=True)
-    assert r.returncode == 0 and "Sanitizer" not in r.stderr, r.stderr[-2000:]
+    hp.run([exe, inp, scr, out, "%x" % bits(c), seed, M])
     lines = iter(open(out).read().splitlines())
     n, answers = len(turn), []
     for op in script:

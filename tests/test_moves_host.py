@@ -7,58 +7,39 @@ Exact rows at 0..8 empties; search rows of mid3, mid4 and special3 with both
 tables at depths 1..4; depth 8 at 6 empties, where the rows are T times the
 exact ones.  The same under -fsanitize=address,undefined, as a process of its
 own.  CPU only."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_programs as hp
 import moves_ref
 import solve_cases
 import tree_cases
 
 from subproc_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tools", "diag", "moves_host.cpp")
 T = moves_ref.T
-
-
-def compiled(tmp_path_factory, name, flags):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.check_call(["g++", "-std=c++17", *flags, "-o", exe, SOURCE])
-    return exe
 
 
 @pytest.fixture(scope="module")
 def binary(tmp_path_factory):
-    return compiled(tmp_path_factory, "moves_host", ["-O2", "-fopenmp"])
+    return hp.compiled(tmp_path_factory, "moves_host")
 
 
 @pytest.fixture(scope="module")
 def binary_asan(tmp_path_factory):
-    return compiled(tmp_path_factory, "moves_host_asan",
-                    ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    return hp.compiled(tmp_path_factory, "moves_host", hp.SANITIZED)
 
 
 def run(binary, tmp_path, mode, boards, turn, level, weights=None, limit=0):
     """(value, move, status, nodes, rows (n, 64)) of the host program."""
     inp, out, wf = str(tmp_path / "in"), str(tmp_path / "out"), str(tmp_path / "w")
-    with open(inp, "w") as f:
-        for (b, w), t in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist()):
-            f.write("%x %x %d\n" % (b, w, t))
+    hp.write_positions(inp, boards, turn)
     args = [binary, mode, inp, out]
     if mode == "search":
-        with open(wf, "w") as f:
-            f.write(" ".join(str(int(x)) for x in np.asarray(weights).reshape(-1)))
+        hp.write_weights(wf, weights)
         args.append(wf)
-    r = subprocess.run(args + [str(level), str(limit), "8"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert "Sanitizer" not in r.stderr, r.stderr[-2000:]
-    a = np.array([[int(x) for x in ln.split()] for ln in open(out)], np.int64).reshape(len(turn), 68)
+    hp.run(args + [level, limit, 8])
+    a = hp.read_rows(out, (len(turn), 68))
     return a[:, 0], a[:, 1], a[:, 2], a[:, 3], a[:, 4:]
 
 

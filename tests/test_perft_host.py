@@ -7,53 +7,33 @@ Splits 0, 1, 3 and 5 and lists of 64, 4,096 and 2**18 tasks, with and without
 the rows, so that void levels occur and deep levels too: leaves, divide and
 status must not depend on any of it.  The same under
 -fsanitize=address,undefined, as a process of its own.  CPU only."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_programs as hp
 import perft_cases
 import perft_ref
 import synthetic_cases
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIAG = os.path.join(ROOT, "tools", "diag")
-SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 SPLITS = (0, 1, 3, 5)
 CAPS = (64, 4096, 1 << 18)  # (the last so that the deep levels are made, not only declared void)
 
 
-def compiled(tmp_path_factory, name, flags):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.check_call(["g++", "-std=c++17", *flags, "-o", exe, os.path.join(DIAG, "perft_host.cpp")])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def binary(tmp_path_factory):
-    return compiled(tmp_path_factory, "perft_host", ["-O2", "-fopenmp"])
+    return hp.compiled(tmp_path_factory, "perft_host")
 
 
 @pytest.fixture(scope="module")
 def binary_asan(tmp_path_factory):
-    return compiled(tmp_path_factory, "perft_host_asan", SAN)
+    return hp.compiled(tmp_path_factory, "perft_host", hp.SANITIZED)
 
 
 def run(exe, tmp, boards, turn, depth, split, max_tasks, divide=1, limit=0, depths=None):
     inp, out = str(tmp / "pin"), str(tmp / "pout")
-    with open(inp, "w") as f:
-        for i, ((b, w), t) in enumerate(zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist())):
-            f.write("%x %x %d" % (b, w, t) + ("\n" if depths is None else " %d\n" % int(depths[i])))
-    r = subprocess.run([exe, inp, out, str(-1 if depths is not None else depth), str(split), str(max_tasks),
-                        str(divide), str(limit), "8"], capture_output=True, text=True)
-    assert r.returncode == 0 and "Sanitizer" not in r.stderr, r.stderr[-2000:]
-    lines = open(out).read().splitlines()
-    a = np.array([[int(x) for x in ln.split()] for ln in lines[:-1]], np.int64).reshape(len(turn), 67)
-    meta = lines[-1].split()
+    hp.write_positions(inp, boards, turn, depths)
+    hp.run([exe, inp, out, -1 if depths is not None else depth, split, max_tasks, divide, limit, 8])
+    a, meta = hp.read_rows(out, (len(turn), 67), trailer=True)
     return dict(leaves=a[:, 0], status=a[:, 1], nodes=a[:, 2], divide=a[:, 3:], levels=int(meta[1]),
                 void=int(meta[3]), tasks=int(meta[5]))
 

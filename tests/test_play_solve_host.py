@@ -16,11 +16,11 @@ import functools
 import numpy as np
 import pytest
 
+import host_programs as hp
 import play_ref
 import play_solve_cases as cases
 import tree_cases
 
-SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 WA, WB = tree_cases.TABLES["default"], tree_cases.TABLES["rng7"]
 ZONES = (1, 5, 8, 9)
 DEPTHS, N_RAND, SEED = (2, 1), (1, 2), 4242
@@ -28,12 +28,12 @@ DEPTHS, N_RAND, SEED = (2, 1), (1, 2), 4242
 
 @pytest.fixture(scope="module")
 def binary(tmp_path_factory):
-    return cases.compiled(tmp_path_factory, "play_solve_host", ["-O2", "-fopenmp"])
+    return cases.compiled(tmp_path_factory)
 
 
 @pytest.fixture(scope="module")
 def binary_asan(tmp_path_factory):
-    return cases.compiled(tmp_path_factory, "play_solve_host_asan", SAN)
+    return cases.compiled(tmp_path_factory, hp.SANITIZED)
 
 
 def arguments(e):

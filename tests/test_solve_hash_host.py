@@ -12,18 +12,17 @@ import ctypes
 import json
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_programs as hp
 import solve_cases
 
 from subproc_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tools", "diag", "solve_hash_host.cpp")
 FIXTURE = os.path.join(ROOT, "tests", "golden", "solve_deep", "solve_deep.npz")
 SOLVED = 1
 SMALLEST = _lib.SOLVE_HASH_MIN_BITS
@@ -33,25 +32,16 @@ THREADS = 8
 
 @pytest.fixture(scope="module")
 def binary(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("solve_hash_host") / "solve_hash_host")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-pthread", "-o", exe, SOURCE])
-    return exe
+    return hp.compiled(tmp_path_factory, "solve_hash_host")
 
 
 def run(binary, tmp_path, mode, boards, turn, max_empties, task_empties, npp, order, bits, gate=1, task_orders=3,
         plain=0):
     """rows [n][runs][value, move, status, nodes] and the program's JSON line."""
     inp, out = str(tmp_path / "in"), str(tmp_path / "out")
-    with open(inp, "w") as f:
-        for (b, w), t in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist()):
-            f.write("%x %x %d\n" % (b, w, t))
-    r = subprocess.run([binary, mode, inp, out, str(max_empties), str(task_empties), str(npp), str(order), str(bits),
-                        str(gate), str(task_orders), str(plain), str(THREADS)], check=True, capture_output=True,
-                       text=True)
-    rows = np.array([[int(x) for x in ln.split()] for ln in open(out)], np.int64)
-    return rows.reshape(len(turn), -1, 4), json.loads(r.stderr.strip().splitlines()[-1])
+    hp.write_positions(inp, boards, turn)
+    r = hp.run([binary, mode, inp, out, max_empties, task_empties, npp, order, bits, gate, task_orders, plain, THREADS])
+    return hp.read_rows(out, (len(turn), -1, 4)), json.loads(r.stderr.strip().splitlines()[-1])
 
 
 def checker_cases(lo, hi):

@@ -4,17 +4,15 @@ shuffled, nothing shared) and both move orders against the exhaustive checker
 (tests/solve_ref.py) at 3..8 empties and against the deep fixture
 (tests/golden/solve_deep/solve_deep.npz) at 13 and 14 empties.  CPU only."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_programs as hp
 import solve_cases
 import solve_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tools", "diag", "solve_tree_host.cpp")
 FIXTURE = os.path.join(ROOT, "tests", "golden", "solve_deep", "solve_deep.npz")
 SOLVED, NOROOM = 1, 4
 DEFAULT_NODES = 65536
@@ -23,23 +21,15 @@ THREADS = 8
 
 @pytest.fixture(scope="module")
 def binary(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp("solve_tree_host") / "solve_tree_host")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fopenmp", "-o", exe, SOURCE])
-    return exe
+    return hp.compiled(tmp_path_factory, "solve_tree_host")
 
 
 def run(binary, tmp_path, boards, turn, max_empties, task_empties, npp, order):
     """(value, move, status), each [4 task orders][n]."""
     inp, out = str(tmp_path / "in"), str(tmp_path / "out")
-    with open(inp, "w") as f:
-        for (b, w), t in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist()):
-            f.write("%x %x %d\n" % (b, w, t))
-    subprocess.run([binary, inp, out, str(max_empties), str(task_empties), str(npp), "0", "7", str(order),
-                    str(THREADS)], check=True, stderr=subprocess.DEVNULL)
-    rows = np.array([[int(x) for x in ln.split()] for ln in open(out)], np.int64).reshape(-1, 4, 4)
-    return tuple(rows[:, :, k].T for k in range(3))
+    hp.write_positions(inp, boards, turn)
+    hp.run([binary, inp, out, max_empties, task_empties, npp, 0, 7, order, THREADS])
+    return hp.read_rows(out, orders=4)[:3]
 
 
 def test_the_default_slab_is_the_bindings():

@@ -11,59 +11,43 @@ a window is never above the full window's.  The same under
 threads on one table under -fsanitize=thread, a table filled by full-window
 solves first and the other way round.  CPU only."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_programs as hp
 import solve_cases
 import window_ref
 
 from subproc_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tools", "diag", "solve_window_host.cpp")
 FIXTURE = os.path.join(ROOT, "tests", "golden", "solve_deep", "solve_deep.npz")
 SOLVED = _lib.SOLVE_SOLVED
 THREADS = 8
 RUNS = ["order %d, %s" % (o, k) for o in (0, 1) for k in ("forward", "reverse", "shuffled", "nothing shared")]
 
 
-def compiled(tmp_path_factory, name, flags):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    exe = str(tmp_path_factory.mktemp(name) / name)
-    subprocess.check_call(["g++", "-std=c++17", "-pthread", *flags, "-o", exe, SOURCE])
-    return exe
-
-
 @pytest.fixture(scope="module")
 def binary(tmp_path_factory):
-    return compiled(tmp_path_factory, "solve_window_host", ["-O2", "-fopenmp"])
+    return hp.compiled(tmp_path_factory, "solve_window_host")
 
 
 @pytest.fixture(scope="module")
 def binary_asan(tmp_path_factory):
-    return compiled(tmp_path_factory, "solve_window_host_asan",
-                    ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    return hp.compiled(tmp_path_factory, "solve_window_host", hp.SANITIZED)
 
 
 @pytest.fixture(scope="module")
 def binary_tsan(tmp_path_factory):
-    return compiled(tmp_path_factory, "solve_window_host_tsan", ["-O1", "-g", "-fsanitize=thread"])
+    return hp.compiled(tmp_path_factory, "solve_window_host", hp.THREAD_SANITIZED)
 
 
 def run(binary, tmp_path, args, boards, turn, alpha, beta):
     inp, out = str(tmp_path / "in"), str(tmp_path / "out")
-    with open(inp, "w") as f:
-        for (b, w), t, lo, hi in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist(),
-                                     np.asarray(alpha).tolist(), np.asarray(beta).tolist()):
-            f.write("%x %x %d %d %d\n" % (b, w, t, lo, hi))
-    r = subprocess.run([binary, args[0], inp, out, *[str(x) for x in args[1:]]], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert "Sanitizer" not in r.stderr, r.stderr[-2000:]
-    return np.array([[int(x) for x in ln.split()] for ln in open(out)], np.int64).reshape(len(turn), -1)
+    hp.write_positions(inp, boards, turn, np.stack([np.asarray(alpha), np.asarray(beta)], axis=1))
+    hp.run([binary, args[0], inp, out, *args[1:]])
+    return hp.read_rows(out, (len(turn), -1))
 
 
 def check_mode_a(rows, value, move, what):

@@ -8,13 +8,10 @@ reverse, shuffled, nothing shared); every driver runs with order 0 and 1.  The
 last three drivers (root windows, the value of every root move, the principal
 variation) run on batches X and S, with the helpers of their own host files.
 CPU only."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_programs as hp
 import oracle
 import play_ref
 import search_ref
@@ -29,7 +26,6 @@ import test_solve_window_host as window_host
 import tree_cases
 import window_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVERS = ("solve", "search", "tree", "solve_tree", "play")
 SOLVED = SEARCHED = 1
 SKIPPED, NOROOM = 0, 4
@@ -209,46 +205,22 @@ def test_the_tied_roots():
 # ---------------------------------------------------------------- the host drivers
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    if shutil.which("g++") is None:
-        pytest.skip("no g++")
-    d = tmp_path_factory.mktemp("synthetic_host")
-    exe = {}
-    for name in DRIVERS:
-        exe[name] = str(d / (name + "_host"))
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fopenmp", "-o", exe[name],
-                               os.path.join(ROOT, "tools", "diag", name + "_host.cpp")])
-    return exe
-
-
-def write_positions(path, boards, turn):
-    with open(path, "w") as f:
-        for (b, w), t in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist()):
-            f.write("%x %x %d\n" % (b, w, t))
-
-
-def write_weights(path, weights):
-    with open(path, "w") as f:
-        f.write(" ".join(str(int(x)) for x in np.asarray(weights).reshape(-1)) + "\n")
-
-
-def read_rows(path, orders):
-    rows = np.array([[int(x) for x in ln.split()] for ln in open(path)], np.int64)
-    if orders == 1:
-        return rows[:, 0], rows[:, 1], rows[:, 2]
-    rows = rows.reshape(-1, orders, 4)
-    return tuple(rows[:, :, k].T for k in range(3))
+    return {name: hp.compiled(tmp_path_factory, name + "_host") for name in DRIVERS}
 
 
 def run_driver(exe, tmp_path, boards, turn, args, weights=None, orders=1):
     """(value, move, status) of a driver: [n], or [4 task orders][n] for the two tree drivers."""
     inp, out, wf = (str(tmp_path / x) for x in ("in", "out", "w"))
-    write_positions(inp, boards, turn)
+    hp.write_positions(inp, boards, turn)
     head = [exe, inp, out]
     if weights is not None:
-        write_weights(wf, weights)
+        hp.write_weights(wf, weights, end="\n")
         head.append(wf)
-    subprocess.run(head + [str(a) for a in args], check=True, stderr=subprocess.DEVNULL)
-    return read_rows(out, orders)
+    hp.run(head + list(args))
+    if orders == 1:
+        rows = hp.read_rows(out)
+        return rows[:, 0], rows[:, 1], rows[:, 2]
+    return hp.read_rows(out, orders=orders)[:3]
 
 
 def solve_host(host, tmp_path, boards, turn, max_empties=12):
@@ -274,20 +246,10 @@ def play_host(host, tmp_path, name, order, boards=None, turn=None, depth=None, e
     if boards is None:
         boards, turn = sc.play_starts(name)
     args, out = str(tmp_path / "args"), str(tmp_path / "out")
-    with open(args, "w") as f:
-        f.write("%d %d %d %d %d %d %d %d %d %d %d\n" % (len(turn), c["seed"], 0, c["depth"][0], c["depth"][1],
-                                                     c["exact"], 0, 0, 1, NODE_LIMIT, 1))
-        for w in ("default", "rng7"):
-            f.write(" ".join(str(int(x)) for x in sc.TABLES[w].reshape(-1)) + "\n")
-        for (b, w), t in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist()):
-            f.write("%x %x %d\n" % (b, w, t))
-    subprocess.run([host["play"], args, out, str(THREADS), str(order)], check=True, stderr=subprocess.DEVNULL)
-    rows = [ln.split() for ln in open(out)]
-    return dict(a_black=np.array([int(r[0]) for r in rows], np.uint8),
-                final_boards=np.array([[int(r[1], 16), int(r[2], 16)] for r in rows], np.uint64).reshape(-1, 2),
-                diff=np.array([int(r[3]) for r in rows], np.int8), plies=np.array([int(r[4]) for r in rows], np.uint8),
-                status=np.array([int(r[5]) for r in rows], np.uint8),
-                moves=np.array([list(bytes.fromhex(r[7])) for r in rows], np.uint8).reshape(-1, 128))
+    hp.write_game_args(args, len(turn), c["seed"], c["depth"], c["exact"], (0, 0), True, NODE_LIMIT,
+                       sc.TABLES["default"], sc.TABLES["rng7"], boards, turn)
+    hp.run([host["play"], args, out, THREADS, order])
+    return hp.read_games(out)
 
 
 def same(got, want, what, status=SOLVED):
@@ -463,17 +425,17 @@ def test_the_checkers_rows_move_with_the_squares():
 
 @pytest.fixture(scope="module")
 def window_exe(tmp_path_factory):
-    return window_host.compiled(tmp_path_factory, "solve_window_host", ["-O2", "-fopenmp"])
+    return hp.compiled(tmp_path_factory, "solve_window_host")
 
 
 @pytest.fixture(scope="module")
 def moves_exe(tmp_path_factory):
-    return moves_host.compiled(tmp_path_factory, "moves_host", ["-O2", "-fopenmp"])
+    return hp.compiled(tmp_path_factory, "moves_host")
 
 
 @pytest.fixture(scope="module")
 def line_exe(tmp_path_factory):
-    return line_host.compiled(tmp_path_factory, "line_host", ["-O2", "-fopenmp"])
+    return hp.compiled(tmp_path_factory, "line_host")
 
 
 def run_windows(exe, tmp_path, rows, task_empties, npp, threads, what):
@@ -605,18 +567,17 @@ def check_per_position(got, b, t, depths, weights):
     assert (line_ref.end_score(got["end_boards"][~off], t[~off], weights) == got["value"][~off]).all()
 
 
-SANITIZED = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 S_DEFAULT_RUNS = [(d, "default") for d in (1, 2, 3)]
 
 
 def test_window_host_under_the_address_and_undefined_behaviour_sanitizers(tmp_path_factory, tmp_path):
-    exe = window_host.compiled(tmp_path_factory, "solve_window_host_asan", SANITIZED)
+    exe = hp.compiled(tmp_path_factory, "solve_window_host", hp.SANITIZED)
     run_windows(exe, tmp_path, slice(None), 3, 4096, 1, "asan")
     run_windows(exe, tmp_path, slice(None), 1, 64, 1, "asan, 64 nodes")
 
 
 def test_moves_host_under_the_address_and_undefined_behaviour_sanitizers(tmp_path_factory, tmp_path):
-    exe = moves_host.compiled(tmp_path_factory, "moves_host_asan", SANITIZED)
+    exe = hp.compiled(tmp_path_factory, "moves_host", hp.SANITIZED)
     b, t = sc.batch_x()
     for level in (8, 12):
         check_exact_rows(moves_host.run(exe, tmp_path, "solve", b, t, level), sc.x_moves(), b, t, ("asan", level))
@@ -624,6 +585,6 @@ def test_moves_host_under_the_address_and_undefined_behaviour_sanitizers(tmp_pat
 
 
 def test_line_host_under_the_address_and_undefined_behaviour_sanitizers(tmp_path_factory, tmp_path):
-    exe = line_host.compiled(tmp_path_factory, "line_host_asan", SANITIZED)
+    exe = hp.compiled(tmp_path_factory, "line_host", hp.SANITIZED)
     check_exact_lines(exe, tmp_path)
     check_search_lines(exe, tmp_path, S_DEFAULT_RUNS)

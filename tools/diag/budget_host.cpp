@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "../../subproc_amd/csrc/budget_core.hpp"
+#include "host_io.hpp"
 #include "host_rules.hpp"
 
 using othm::u32;
@@ -33,20 +34,6 @@ using othm::u64;
 
 using HostStack = HostStack9<othm::kFrames>;
 
-static bool read_weights(FILE* f, int8_t* w36) {
-    for (int k = 0; k < othm::kEvalPhases * othm::kEvalFeatures; k++) {
-        int v;
-        if (fscanf(f, "%d", &v) != 1 || v < -128 || v > 127) return false;
-        w36[k] = (int8_t)v;
-    }
-    return true;
-}
-
-struct Pos {
-    u64 black, white;
-    int turn;
-    u32 budget;
-};
 struct SearchOut {
     int value;
     u32 best, status, depth, nodes;
@@ -60,9 +47,8 @@ static SearchOut search_one(const Pos& p, int cap, const int* table) {
     othm::Order Q;
     othm::order_reset(Q);
     othb::Deepen D{};
-    const bool white = p.turn == 2;
-    const u64 P = white ? p.white : p.black, O = white ? p.black : p.white;
-    othb::begin_search<HostRules>(D, L, P, O, p.budget, cap);
+    const u64 P = p.mover(), O = p.other();
+    othb::begin_search<HostRules>(D, L, P, O, (u32)p.extra[0], cap);
     if (L.depth >= 0)
         while (!othb::advance_search<HostRules, kOrdered>(D, L, Q, stk, table, P, O)) {
         }
@@ -75,38 +61,22 @@ static int main_search(int argc, char** argv) {
     const int order = argc > 6 ? atoi(argv[6]) : 0;
     const int threads = argc > 7 ? atoi(argv[7]) : 16;
     if (cap < 1 || cap > othm::kMaxDepth || threads < 1 || order < 0 || order > 1) return 2;
-    FILE* wf = fopen(argv[4], "r");
-    if (!wf) return 1;
-    int8_t w36[othm::kEvalPhases * othm::kEvalFeatures];
-    if (!read_weights(wf, w36)) return 2;
-    fclose(wf);
     int table[othm::kEvalTable];
-    for (int e = 0; e < othm::kEvalTable; e++) othm::widen_weight(w36, e, table);
-    FILE* in = fopen(argv[2], "r");
-    if (!in) return 1;
+    read_weights(argv[4], table);
     std::vector<Pos> pos;
-    unsigned long long b, w, budget;
-    int t;
-    while (fscanf(in, "%llx %llx %d %llu", &b, &w, &t, &budget) == 4) {
-        if (budget > 0xFFFFFFFFull) return 2;
-        pos.push_back(Pos{b, w, t, (u32)budget});
-    }
-    fclose(in);
+    read_positions(argv[2], 1, pos);
+    for (const Pos& p : pos)
+        if (p.extra[0] > 0xFFFFFFFFull) return 2;
     std::vector<SearchOut> out(pos.size());
     const long n = (long)pos.size();
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
     for (long i = 0; i < n; i++) out[i] = order ? search_one<true>(pos[i], cap, table) : search_one<false>(pos[i], cap, table);
-    FILE* o = fopen(argv[3], "w");
-    if (!o) return 1;
+    FILE* o = open_or_exit(argv[3], "w");
     for (const SearchOut& r : out) fprintf(o, "%d %u %u %u %u\n", r.value, r.best, r.status, r.depth, r.nodes);
     fclose(o);
     return 0;
 }
 
-struct Start {
-    u64 black, white;
-    int turn;
-};
 struct GameOut {
     int a_black, diff;
     u64 black, white, nodes;
@@ -118,7 +88,7 @@ struct GameOut {
 };
 
 template <bool kOrdered>
-static void play_one(const Start& s, u64 key, const othp::Match& m, const othb::Budgets& bud, const int* tables,
+static void play_one(const Pos& s, u64 key, const othp::Match& m, const othb::Budgets& bud, const int* tables,
                      GameOut& out) {
     memset(out.moves, 255, sizeof out.moves);
     othp::Game G;
@@ -144,8 +114,7 @@ static int main_play(int argc, char** argv) {
     const int order = argc > 4 ? atoi(argv[4]) : 0;
     const int threads = argc > 5 ? atoi(argv[5]) : 16;
     if (threads < 1 || order < 0 || order > 1) return 2;
-    FILE* in = fopen(argv[2], "r");
-    if (!in) return 1;
+    FILE* in = open_or_exit(argv[2], "r");
     long n;
     unsigned long long seed, id0, limit_arg, ba, bb;
     int da, db, exact, ra, rb, swap, have_start;
@@ -156,19 +125,15 @@ static int main_play(int argc, char** argv) {
         exact > othm::kMaxDepth || ra < 0 || rb < 0 || limit_arg > 0xFFFFFFFFull || ba < 1 || ba > 0xFFFFFFFFull ||
         bb < 1 || bb > 0xFFFFFFFFull)
         return 2;
-    int8_t w36[2][othm::kEvalPhases * othm::kEvalFeatures];
-    if (!read_weights(in, w36[0]) || !read_weights(in, w36[1])) return 2;
     int tables[2 * othm::kEvalTable];
-    for (int p = 0; p < 2; p++)
-        for (int e = 0; e < othm::kEvalTable; e++) othm::widen_weight(w36[p], e, tables + p * othm::kEvalTable);
-    std::vector<Start> starts((size_t)n, Start{othp::kOpenBlack, othp::kOpenWhite, 1});
-    if (have_start)
-        for (long i = 0; i < n; i++) {
-            unsigned long long b, w;
-            int t;
-            if (fscanf(in, "%llx %llx %d", &b, &w, &t) != 3) return 2;
-            starts[(size_t)i] = Start{b, w, t};
-        }
+    if (!read_weights(in, tables) || !read_weights(in, tables + othm::kEvalTable)) return 2;
+    std::vector<Pos> starts;
+    if (have_start) {
+        read_positions(in, 0, starts, n);
+        if ((long)starts.size() != n) return 2;
+    } else {
+        starts.assign((size_t)n, Pos{othp::kOpenBlack, othp::kOpenWhite, 1, {0, 0}});
+    }
     fclose(in);
     othp::Match m;
     m.depth[0] = da;
@@ -176,7 +141,7 @@ static int main_play(int argc, char** argv) {
     m.n_rand[0] = (u32)(ra < (int)othp::kMaxBudget ? ra : (int)othp::kMaxBudget);
     m.n_rand[1] = (u32)(rb < (int)othp::kMaxBudget ? rb : (int)othp::kMaxBudget);
     m.exact_empties = exact;
-    m.limit = limit_arg ? (u32)limit_arg : (1u << 28);
+    m.limit = node_limit(limit_arg);
     m.swap = swap != 0;
     othb::Budgets bud;
     bud.budget[0] = (u32)ba;
@@ -191,8 +156,7 @@ static int main_play(int argc, char** argv) {
         else
             play_one<false>(starts[(size_t)i], key, m, bud, tables, out[(size_t)i]);
     }
-    FILE* o = fopen(argv[3], "w");
-    if (!o) return 1;
+    FILE* o = open_or_exit(argv[3], "w");
     for (const GameOut& r : out) {
         fprintf(o, "%d %llx %llx %d %u %u %llu ", r.a_black, (unsigned long long)r.black, (unsigned long long)r.white,
                 r.diff, r.plies, r.status, (unsigned long long)r.nodes);

@@ -1,7 +1,8 @@
-// host_rules.hpp — what the host builds of the searches (solve_host.cpp,
-// search_host.cpp, play_host.cpp, tree_host.cpp, solve_tree_host.cpp) give the
-// cores in place of the device's parameters: a plain C++ statement of the rules
-// (R), plain loads and stores for the atomics (A) and arrays for the frames (S).
+// host_rules.hpp — what every host build of the cores (tools/diag/*_host.cpp;
+// tools/diag/README.md lists them) gives the cores in place of the device's
+// parameters: a plain C++ statement of the rules (R), plain loads and stores for
+// the atomics (A) and arrays for the frames (S).  The files the programs read
+// are host_io.hpp's.
 #pragma once
 #include <stdint.h>
 

@@ -21,16 +21,11 @@
 #include <vector>
 
 #include "../../subproc_amd/csrc/line_core.hpp"
+#include "host_io.hpp"
 #include "host_rules.hpp"
 
 using othm::u32;
 using othm::u64;
-
-struct Pos {
-    u64 black, white;
-    int turn;
-    u32 depth;
-};
 
 struct LineOut {
     int value;
@@ -57,8 +52,8 @@ struct LineOut {
 
 static void solve_one(const Pos& p, int max_empties, u32 limit, LineOut& out) {
     out.clear(0);
-    const bool white = p.turn == 2;
-    const u64 P = white ? p.white : p.black, O = white ? p.black : p.white;
+    const bool white = p.white_to_move();
+    const u64 P = p.mover(), O = p.other();
     const u32 st = oths::classify(p.black, p.white, 64 - HostRules::count(p.black | p.white), max_empties);
     othl::Walk W;
     if (st != oths::kSolved) {
@@ -75,11 +70,11 @@ static void solve_one(const Pos& p, int max_empties, u32 limit, LineOut& out) {
 }
 
 template <bool kOrdered>
-static void search_one(const Pos& p, const int* table, u32 limit, LineOut& out) {
+static void search_one(const Pos& p, u32 depth, const int* table, u32 limit, LineOut& out) {
     out.clear(0);
-    const bool white = p.turn == 2;
-    const u64 P = white ? p.white : p.black, O = white ? p.black : p.white;
-    const u32 st = (p.black & p.white) ? othm::kInvalid : othl::classify_depth(p.depth);
+    const bool white = p.white_to_move();
+    const u64 P = p.mover(), O = p.other();
+    const u32 st = (p.black & p.white) ? othm::kInvalid : othl::classify_depth(depth);
     othl::Walk W;
     if (st != othm::kSearched) {
         othl::open(W, P, O, 0, st);
@@ -88,7 +83,7 @@ static void search_one(const Pos& p, const int* table, u32 limit, LineOut& out) 
     othm::Lane L;
     HostStack9<othm::kFrames> stk;
     othm::Order Q;
-    othl::begin_search(W, L, P, O, (int)p.depth);
+    othl::begin_search(W, L, P, O, (int)depth);
     do {
         othm::order_reset(Q);
         while (L.depth >= 0) {
@@ -101,23 +96,8 @@ static void search_one(const Pos& p, const int* table, u32 limit, LineOut& out) 
     out.finish(W, white);
 }
 
-static bool read_positions(const char* path, bool with_depth, u32 depth, std::vector<Pos>& pos) {
-    FILE* in = fopen(path, "r");
-    if (!in) return false;
-    unsigned long long b, w;
-    int t;
-    while (fscanf(in, "%llx %llx %d", &b, &w, &t) == 3) {
-        unsigned d = depth;
-        if (with_depth && fscanf(in, "%u", &d) != 1) return false;
-        pos.push_back(Pos{b, w, t, d});
-    }
-    fclose(in);
-    return true;
-}
-
-static bool write_out(const char* path, const std::vector<LineOut>& out) {
-    FILE* o = fopen(path, "w");
-    if (!o) return false;
+static int write_out(const char* path, const std::vector<LineOut>& out) {
+    FILE* o = open_or_exit(path, "w");
     for (const LineOut& r : out) {
         fprintf(o, "%d %u %u %u %u %llx %llx %d ", r.value, r.best, r.status, r.nodes, r.length,
                 (unsigned long long)r.black, (unsigned long long)r.white, r.end_turn);
@@ -125,7 +105,7 @@ static bool write_out(const char* path, const std::vector<LineOut>& out) {
         fprintf(o, "\n");
     }
     fclose(o);
-    return true;
+    return 0;
 }
 
 static int main_solve(int argc, char** argv) {
@@ -134,14 +114,14 @@ static int main_solve(int argc, char** argv) {
     const unsigned long long limit_arg = argc > 5 ? strtoull(argv[5], nullptr, 10) : 0;
     const int threads = argc > 6 ? atoi(argv[6]) : 16;
     if (max_empties < 0 || max_empties > oths::kMaxEmpties || limit_arg > 0xFFFFFFFFull || threads < 1) return 2;
-    const u32 limit = limit_arg ? (u32)limit_arg : (1u << 28);
+    const u32 limit = node_limit(limit_arg);
     std::vector<Pos> pos;
-    if (!read_positions(argv[2], false, 0, pos)) return 1;
+    read_positions(argv[2], 0, pos);
     std::vector<LineOut> out(pos.size());
     const long n = (long)pos.size();
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
     for (long i = 0; i < n; i++) solve_one(pos[(size_t)i], max_empties, limit, out[(size_t)i]);
-    return write_out(argv[3], out) ? 0 : 1;
+    return write_out(argv[3], out);
 }
 
 static int main_search(int argc, char** argv) {
@@ -153,30 +133,23 @@ static int main_search(int argc, char** argv) {
     if ((depth != -1 && (depth < 1 || depth > othm::kMaxDepth)) || order < 0 || order > 1 ||
         limit_arg > 0xFFFFFFFFull || threads < 1)
         return 2;
-    const u32 limit = limit_arg ? (u32)limit_arg : (1u << 28);
-    FILE* wf = fopen(argv[4], "r");
-    if (!wf) return 1;
-    int8_t w36[othm::kEvalPhases * othm::kEvalFeatures];
-    for (int k = 0; k < othm::kEvalPhases * othm::kEvalFeatures; k++) {
-        int v;
-        if (fscanf(wf, "%d", &v) != 1 || v < -128 || v > 127) return 2;
-        w36[k] = (int8_t)v;
-    }
-    fclose(wf);
+    const u32 limit = node_limit(limit_arg);
     int table[othm::kEvalTable];
-    for (int e = 0; e < othm::kEvalTable; e++) othm::widen_weight(w36, e, table);
+    read_weights(argv[4], table);
     std::vector<Pos> pos;
-    if (!read_positions(argv[2], depth == -1, depth == -1 ? 0u : (u32)depth, pos)) return 1;
+    if (read_positions(argv[2], depth == -1, pos) == 3) return 1;  // a line without its depth
     std::vector<LineOut> out(pos.size());
     const long n = (long)pos.size();
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
     for (long i = 0; i < n; i++) {
+        const Pos& p = pos[(size_t)i];
+        const u32 d = depth == -1 ? (u32)p.extra[0] : (u32)depth;
         if (order)
-            search_one<true>(pos[(size_t)i], table, limit, out[(size_t)i]);
+            search_one<true>(p, d, table, limit, out[(size_t)i]);
         else
-            search_one<false>(pos[(size_t)i], table, limit, out[(size_t)i]);
+            search_one<false>(p, d, table, limit, out[(size_t)i]);
     }
-    return write_out(argv[3], out) ? 0 : 1;
+    return write_out(argv[3], out);
 }
 
 int main(int argc, char** argv) {

@@ -24,12 +24,9 @@
 #include <cstring>
 #include <vector>
 
+#include "host_io.hpp"
 #include "mcts_host_common.hpp"
 
-struct Pos {
-    u64 black, white;
-    int turn;
-};
 struct Row {
     u32 status = othu::kInvalid, best = othu::kNoMove, nodes = 0, root_wins = 0;
     int root_diffs = 0;
@@ -38,10 +35,7 @@ struct Row {
 };
 
 int main(int argc, char** argv) {
-    if (argc < 8) {
-        fprintf(stderr, "usage: %s IN OUT iterations explore_bits seed game_id0 max_nodes [threads=16]\n", argv[0]);
-        return 2;
-    }
+    if (argc < 8) usage(argv[0], "IN OUT iterations explore_bits seed game_id0 max_nodes [threads=16]");
     const long T = atol(argv[3]);
     const u32 cbits = (u32)strtoul(argv[4], nullptr, 16);
     const u64 seed = strtoull(argv[5], nullptr, 0), game_id0 = strtoull(argv[6], nullptr, 0);
@@ -50,24 +44,9 @@ int main(int argc, char** argv) {
     if (T < 1 || T > (long)othu::kMaxIterations || M < 1 || M > (long)othu::kMaxNodes || threads < 1) return 2;
     float c;
     memcpy(&c, &cbits, 4);
-    FILE* in = fopen(argv[1], "r");
-    if (!in) return 1;
     std::vector<Pos> pos;
     std::vector<float> table;
-    char line[256];
-    while (fgets(line, sizeof line, in)) {
-        unsigned long long b, w;
-        unsigned bits;
-        int t;
-        if (sscanf(line, "L %x", &bits) == 1) {
-            float f;
-            memcpy(&f, &bits, 4);
-            table.push_back(f);
-        } else if (sscanf(line, "%llx %llx %d", &b, &w, &t) == 3) {
-            pos.push_back(Pos{b, w, t});
-        }
-    }
-    fclose(in);
+    read_trees(argv[1], 0, pos, table);
     if ((long)table.size() != T + 1) return 2;
     const long n = (long)pos.size();
     std::vector<Row> rows(n);
@@ -85,8 +64,7 @@ int main(int argc, char** argv) {
         const Pos& q = pos[i];
         Row& r = rows[i];
         if (q.black & q.white) continue;
-        const bool white = q.turn == 2;
-        const u64 P = white ? q.white : q.black, O = white ? q.black : q.white;
+        const u64 P = q.mover(), O = q.other();
         HostTree tree((u32)M);
         HostWave wave;
         r.nodes = othu::search<Rules>(tree, wave, P, O, (u64)i, p);
@@ -103,8 +81,7 @@ int main(int argc, char** argv) {
         r.root_diffs = -tree.d(0);
         r.status = othu::kSearched;
     }
-    FILE* o = fopen(argv[2], "w");
-    if (!o) return 1;
+    FILE* o = open_or_exit(argv[2], "w");
     for (long i = 0; i < n; i++) {
         const Row& r = rows[i];
         fprintf(o, "%u %u %u %u %d", r.status, r.best, r.nodes, r.root_wins, r.root_diffs);

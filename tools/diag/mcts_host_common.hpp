@@ -3,14 +3,35 @@
 // arrays for the tree, loops for the wave's collectives and a plain C++ random
 // playout over DESIGN.md §4's draws.
 #pragma once
+#include <cstring>
 #include <vector>
 
 #include "../../subproc_amd/csrc/mcts_core.hpp"
 #include "../../subproc_amd/csrc/play_core.hpp"  // DESIGN.md §4's draws: seed_state, game_key, Rng
+#include "host_io.hpp"
 #include "host_rules.hpp"
 
 typedef uint64_t u64;
 typedef uint32_t u32;
+
+// the IN file of both programs: positions with `extras` extra columns (a line
+// short of them is passed over), and the table as lines "L <float32 bits hex>"
+static void read_trees(const char* path, int extras, std::vector<Pos>& pos, std::vector<float>& table) {
+    FILE* in = open_or_exit(path, "r");
+    char line[4096];
+    while (fgets(line, sizeof line, in)) {
+        unsigned bits;
+        Pos p;
+        if (sscanf(line, "L %x", &bits) == 1) {
+            float f;
+            memcpy(&f, &bits, 4);
+            table.push_back(f);
+        } else if (parse_position(line, p) >= 3 + extras) {
+            pos.push_back(p);
+        }
+    }
+    fclose(in);
+}
 
 struct Rules : HostRules {
     static u32 kth(u64 m, u32 k) {

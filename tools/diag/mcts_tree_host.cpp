@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/othello_mcts_tree.h"
+#include "host_io.hpp"
 #include "mcts_host_common.hpp"
 
 struct Tree {
@@ -46,11 +47,6 @@ struct Tree {
     u64 id_base = 0, played = 0;
     u32 count = 0, turn = 1, status = OTHR_INVALID, ran = 0;
     explicit Tree(u32 M) : nodes(M), half(M) {}
-};
-
-struct Start {
-    u64 black, white, id_base;
-    int turn;
 };
 
 static u32 best_move(Tree& t, u32* visits, u32* wins, int* diffs) {
@@ -106,34 +102,17 @@ static void print_dump(FILE* o, Tree& t) {
 }
 
 int main(int argc, char** argv) {
-    if (argc != 7) {
-        fprintf(stderr, "usage: %s IN SCRIPT OUT explore_bits seed max_nodes\n", argv[0]);
-        return 2;
-    }
+    if (argc != 7) usage(argv[0], "IN SCRIPT OUT explore_bits seed max_nodes");
     const u32 cbits = (u32)strtoul(argv[4], nullptr, 16);
     const u64 seed = strtoull(argv[5], nullptr, 0);
     const long M = atol(argv[6]);
     if (M < 1 || M > (long)othu::kMaxNodes) return 2;
     float c;
     memcpy(&c, &cbits, 4);
-    FILE* in = fopen(argv[1], "r");
-    if (!in) return 1;
-    std::vector<Start> starts;
+    std::vector<Pos> starts;  // extra[0]: the tree's id base
     std::vector<float> table;
+    read_trees(argv[1], 1, starts, table);
     char line[4096];
-    while (fgets(line, sizeof line, in)) {
-        unsigned long long b, w, id;
-        unsigned bits;
-        int t;
-        if (sscanf(line, "L %x", &bits) == 1) {
-            float f;
-            memcpy(&f, &bits, 4);
-            table.push_back(f);
-        } else if (sscanf(line, "%llx %llx %d %llu", &b, &w, &t, &id) == 4) {
-            starts.push_back(Start{b, w, id, t});
-        }
-    }
-    fclose(in);
     if (table.size() < 2) return 2;
     const size_t n = starts.size();
     std::vector<Tree> trees(n, Tree((u32)M));
@@ -157,10 +136,10 @@ int main(int argc, char** argv) {
         if (op == "init") {
             for (size_t i = 0; i < n; i++) {
                 Tree& t = trees[i];
-                const Start& s = starts[i];
-                const bool white = s.turn == 2, valid = (s.black & s.white) == 0;
-                othu::init_root(t.nodes, wave, white ? s.white : s.black, white ? s.black : s.white);
-                t.id_base = s.id_base, t.played = 0, t.ran = 0;
+                const Pos& s = starts[i];
+                const bool white = s.white_to_move(), valid = (s.black & s.white) == 0;
+                othu::init_root(t.nodes, wave, s.mover(), s.other());
+                t.id_base = s.extra[0], t.played = 0, t.ran = 0;
                 t.count = valid ? 1u : 0u;
                 t.turn = white ? 2u : 1u;
                 t.status = valid ? OTHR_READY : OTHR_INVALID;

@@ -26,6 +26,7 @@
 
 #include "../../subproc_amd/csrc/search_core.hpp"
 #include "../../subproc_amd/csrc/solve_core.hpp"
+#include "host_io.hpp"
 #include "host_rules.hpp"
 
 typedef uint64_t u64;
@@ -34,10 +35,6 @@ typedef uint32_t u32;
 constexpr u32 kDone = 1, kInvalid = 2, kSkipped = 0, kNoMove = 255, kPass = 64;
 enum Kind { kMoves, kPassed, kOver, kBad, kSkip };
 
-struct Pos {
-    u64 black, white;
-    int turn;
-};
 // a task: X to move against Y, the root mover's discs; sq the root move, 64 for the pass, 255 for an unused slot
 struct Task {
     u64 X, Y;
@@ -59,8 +56,7 @@ static Root expand(const Pos& p, int max_empties /* < 0: the search, no empties 
         r.kind = kSkip;
         return r;
     }
-    const bool white = p.turn == 2;
-    const u64 P = white ? p.white : p.black, O = white ? p.black : p.white;
+    const u64 P = p.mover(), O = p.other();
     u64 M = HostRules::moves(P, O);
     if (M == 0) {
         if (HostRules::moves(O, P) == 0) {
@@ -156,30 +152,14 @@ int main(int argc, char** argv) {
     const int level = atoi(argv[opt - 1]);  // max_empties or depth
     const u32 limit_arg = argc > opt ? (u32)strtoul(argv[opt], nullptr, 0) : 0u;
     const int threads = argc > opt + 1 ? atoi(argv[opt + 1]) : 16;
-    const u32 limit = limit_arg ? limit_arg : (1u << 28);
+    const u32 limit = node_limit(limit_arg);
     if (threads < 1 || (solve && (level < 0 || level > oths::kMaxEmpties)) ||
         (search && (level < 1 || level > othm::kMaxDepth)))
         return 2;
     int table[othm::kEvalTable] = {0};
-    if (search) {
-        FILE* wf = fopen(argv[4], "r");
-        if (!wf) return 1;
-        int8_t w36[othm::kEvalPhases * othm::kEvalFeatures];
-        for (int8_t& w : w36) {
-            int v;
-            if (fscanf(wf, "%d", &v) != 1 || v < -128 || v > 127) return 2;
-            w = (int8_t)v;
-        }
-        fclose(wf);
-        for (int e = 0; e < othm::kEvalTable; e++) othm::widen_weight(w36, e, table);
-    }
-    FILE* in = fopen(argv[2], "r");
-    if (!in) return 1;
+    if (search) read_weights(argv[4], table);
     std::vector<Pos> pos;
-    unsigned long long b, w;
-    int t;
-    while (fscanf(in, "%llx %llx %d", &b, &w, &t) == 3) pos.push_back(Pos{b, w, t});
-    fclose(in);
+    read_positions(argv[2], 0, pos);
     const size_t n = pos.size();
     std::vector<Root> roots(n);
     std::vector<Task> tasks;
@@ -213,8 +193,7 @@ int main(int argc, char** argv) {
             search_task(tk, level, table, limit);
         }
     }
-    FILE* o = fopen(argv[3], "w");
-    if (!o) return 1;
+    FILE* o = open_or_exit(argv[3], "w");
     for (size_t i = 0; i < n; i++) {
         if (solve)
             finish(pos[i], roots[i], tasks.data() + roots[i].first, 1, -128, -127, o);

@@ -13,7 +13,6 @@ parts: search versus end ties play tree ratio (default: all but ratio, which
 runs the 4,096 roots at depth 5 and wants the optimised build: SUFFIX "")
 """
 import os
-import subprocess
 import sys
 import tempfile
 import time
@@ -23,6 +22,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.dirname(os.path.abspath(__file__))]
 
+import host_programs as hp  # noqa: E402
 import order_cases  # noqa: E402
 import play_host_check  # noqa: E402
 import search_ref  # noqa: E402
@@ -38,14 +38,10 @@ def search(binary, boards, turn, depth, weights, order, node_limit=LIMIT, thread
     """(value, move, status, nodes) of search_host."""
     with tempfile.TemporaryDirectory() as d:
         inp, out, wf = (os.path.join(d, x) for x in ("in", "out", "w"))
-        with open(inp, "w") as f:
-            for (b, w), t in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist()):
-                f.write("%x %x %d\n" % (b, w, t))
-        with open(wf, "w") as f:
-            f.write(" ".join(str(int(x)) for x in np.asarray(weights).reshape(-1)) + "\n")
-        subprocess.run([binary, inp, out, wf, str(depth), str(node_limit), str(threads), str(order)], check=True,
-                       stderr=subprocess.DEVNULL)
-        rows = np.array([[int(x) for x in ln.split()] for ln in open(out)], np.int64).reshape(-1, 4)
+        hp.write_positions(inp, boards, turn)
+        hp.write_weights(wf, weights, end="\n")
+        hp.run([binary, inp, out, wf, depth, node_limit, threads, order])
+        rows = hp.read_rows(out, (-1, 4))
     return rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3]
 
 
@@ -53,25 +49,14 @@ def tree(binary, boards, turn, weights, depth, split, npp, order):
     """tree_host_check.run with the order argument: (value, move, status, nodes), each [4 task orders][n]."""
     with tempfile.TemporaryDirectory() as d:
         inp, out, wf = (os.path.join(d, x) for x in ("in", "out", "w"))
-        with open(inp, "w") as f:
-            for (b, w), t in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist()):
-                f.write("%x %x %d\n" % (b, w, t))
-        with open(wf, "w") as f:
-            f.write(" ".join(str(int(x)) for x in np.asarray(weights).reshape(-1)) + "\n")
-        subprocess.run([binary, inp, out, wf, str(depth), str(split), str(npp), str(1 << 22), "1", str(order)],
-                       check=True)
-        rows = np.array([[int(x) for x in ln.split()] for ln in open(out)], np.int64).reshape(-1, 4, 4)
-    return tuple(rows[:, :, k].T for k in range(4))
+        hp.write_positions(inp, boards, turn)
+        hp.write_weights(wf, weights, end="\n")
+        sys.stderr.write(hp.run([binary, inp, out, wf, depth, split, npp, 1 << 22, 1, order]).stderr)
+        return hp.read_rows(out, orders=4)
 
 
 def play(binary, c, boards, turn, order, threads=8, tables=order_cases.TABLES):
-    with tempfile.TemporaryDirectory() as d:
-        args, out = os.path.join(d, "args"), os.path.join(d, "out")
-        play_host_check.write_args(args, c["n"], c["seed"], c["game_id0"], c["depth"], c["exact"], c["n_rand"],
-                                   c["swap"], 1 << 22, tables[c["tables"][0]], tables[c["tables"][1]],
-                                   boards, turn)
-        subprocess.run([binary, args, out, str(threads), str(order)], check=True, stderr=subprocess.DEVNULL)
-        return play_host_check.read_out(out)
+    return play_host_check.play(binary, c, boards, turn, tables, threads, order)
 
 
 def report(label, ok, extra=""):

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../subproc_amd/csrc/perft_core.hpp"
+#include "host_io.hpp"
 #include "host_rules.hpp"
 
 typedef uint64_t u64;
@@ -40,10 +41,6 @@ struct HostStack6 {
     void load(int d, u64& p, u64& o, u64& m) const { p = P[d], o = O[d], m = M[d]; }
 };
 
-struct Pos {
-    u64 black, white;
-    int turn, depth;
-};
 struct Task {
     u64 P, O, word;
 };
@@ -72,29 +69,26 @@ static void expand(const Task& t, std::vector<Task>& out) {
 }
 
 int main(int argc, char** argv) {
-    if (argc < 6) {
-        fprintf(stderr, "usage: %s IN OUT depth split max_tasks [divide=1] [node_limit=0] [threads=16]\n", argv[0]);
-        return 2;
-    }
+    if (argc < 6) usage(argv[0], "IN OUT depth split max_tasks [divide=1] [node_limit=0] [threads=16]");
     const int depth = atoi(argv[3]), split = atoi(argv[4]);
     const long max_tasks = atol(argv[5]);
     const bool divide = argc > 6 ? atoi(argv[6]) != 0 : true;
     const u32 limit_arg = argc > 7 ? (u32)strtoul(argv[7], nullptr, 0) : 0u;
     const int threads = argc > 8 ? atoi(argv[8]) : 16;
-    const u32 limit = limit_arg ? limit_arg : (1u << 28);
+    const u32 limit = node_limit(limit_arg);
     if (depth > othc::kMaxDepth || split < 0 || split > 8 || max_tasks < 0 || max_tasks > (1l << 24) || threads < 1)
         return 2;
-    FILE* in = fopen(argv[1], "r");
-    if (!in) return 1;
+    FILE* in = open_or_exit(argv[1], "r");
     std::vector<Pos> pos;
+    std::vector<int> depths;  // each position's own, or the command line's
     char line[256];
     while (fgets(line, sizeof line, in)) {
-        unsigned long long b, w;
-        int t, d = 0;
-        const int got = sscanf(line, "%llx %llx %d %d", &b, &w, &t, &d);
+        Pos p;
+        const int got = parse_position(line, p);
         if (got < 3) continue;
         if (depth < 0 && got < 4) return 2;
-        pos.push_back(Pos{b, w, t, depth < 0 ? d : depth});
+        pos.push_back(p);
+        depths.push_back(depth < 0 ? (int)p.extra[0] : depth);
     }
     fclose(in);
     const size_t n = pos.size();
@@ -106,10 +100,8 @@ int main(int argc, char** argv) {
     std::vector<Task> list, next;
     for (size_t i = 0; i < n; i++) {
         const Pos& p = pos[i];
-        if ((p.black & p.white) || p.depth < 0 || p.depth > othc::kMaxDepth) continue;
-        const bool white = p.turn == 2;
-        list.push_back(Task{white ? p.white : p.black, white ? p.black : p.white,
-                            othc::task_word(i, othc::kSqNone, (u32)p.depth, false)});
+        if ((p.black & p.white) || depths[i] < 0 || depths[i] > othc::kMaxDepth) continue;
+        list.push_back(Task{p.mover(), p.other(), othc::task_word(i, othc::kSqNone, (u32)depths[i], false)});
     }
     int made = 0, first_void = 0;
     for (int k = 1; k <= levels; k++) {
@@ -162,14 +154,13 @@ int main(int argc, char** argv) {
         }
     }
 
-    FILE* o = fopen(argv[2], "w");
-    if (!o) return 1;
+    FILE* o = open_or_exit(argv[2], "w");
     for (size_t i = 0; i < n; i++) {
         const Pos& p = pos[i];
-        const u32 st = (p.black & p.white)                            ? othc::kInvalid
-                       : (p.depth < 0 || p.depth > othc::kMaxDepth)   ? othc::kBadDepth
-                       : hit[i]                                       ? othc::kLimit
-                                                                      : othc::kCounted;
+        const u32 st = (p.black & p.white)                              ? othc::kInvalid
+                       : (depths[i] < 0 || depths[i] > othc::kMaxDepth) ? othc::kBadDepth
+                       : hit[i]                                         ? othc::kLimit
+                                                                        : othc::kCounted;
         fprintf(o, "%llu %u %llu", (unsigned long long)(hit[i] ? 0 : leaves[i]), st, (unsigned long long)nodes[i]);
         for (int s = 0; s < 64; s++) fprintf(o, " %llu", (unsigned long long)(hit[i] ? 0 : row[i * 64 + s]));
         fprintf(o, "\n");

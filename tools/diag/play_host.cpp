@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../subproc_amd/csrc/play_core.hpp"
+#include "host_io.hpp"
 #include "host_rules.hpp"
 
 using othm::u32;
@@ -32,10 +33,6 @@ using othm::u64;
 
 using HostStack = HostStack9<othm::kFrames>;
 
-struct Start {
-    u64 black, white;
-    int turn;
-};
 struct Out {
     int a_black, diff;
     u64 black, white, nodes;
@@ -46,7 +43,7 @@ struct Out {
     }
 };
 
-static void play_one(const Start& s, u64 key, const othp::Match& m, const int* tables, int order, Out& out) {
+static void play_one(const Pos& s, u64 key, const othp::Match& m, const int* tables, int order, Out& out) {
     memset(out.moves, 255, sizeof out.moves);
     othp::Game G;
     othm::Lane L;
@@ -67,25 +64,12 @@ static void play_one(const Start& s, u64 key, const othp::Match& m, const int* t
     out.nodes = G.nodes;
 }
 
-static bool read_weights(FILE* f, int8_t* w36) {
-    for (int k = 0; k < othm::kEvalPhases * othm::kEvalFeatures; k++) {
-        int v;
-        if (fscanf(f, "%d", &v) != 1 || v < -128 || v > 127) return false;
-        w36[k] = (int8_t)v;
-    }
-    return true;
-}
-
 int main(int argc, char** argv) {
-    if (argc < 3) {
-        fprintf(stderr, "usage: %s ARGS OUT [threads] [order]\n", argv[0]);
-        return 2;
-    }
+    if (argc < 3) usage(argv[0], "ARGS OUT [threads] [order]");
     const int threads = argc > 3 ? atoi(argv[3]) : 16;
     const int order = argc > 4 ? atoi(argv[4]) : 0;
     if (threads < 1 || order < 0 || order > 1) return 2;
-    FILE* in = fopen(argv[1], "r");
-    if (!in) return 1;
+    FILE* in = open_or_exit(argv[1], "r");
     long n;
     unsigned long long seed, id0, limit_arg;
     int da, db, exact, ra, rb, swap, have_start;
@@ -95,19 +79,15 @@ int main(int argc, char** argv) {
     if (n < 0 || da < 1 || da > othm::kMaxDepth || db < 1 || db > othm::kMaxDepth || exact < 0 ||
         exact > othm::kMaxDepth || ra < 0 || rb < 0 || limit_arg > 0xFFFFFFFFull)
         return 2;
-    int8_t w36[2][othm::kEvalPhases * othm::kEvalFeatures];
-    if (!read_weights(in, w36[0]) || !read_weights(in, w36[1])) return 2;
     int tables[2 * othm::kEvalTable];
-    for (int p = 0; p < 2; p++)
-        for (int e = 0; e < othm::kEvalTable; e++) othm::widen_weight(w36[p], e, tables + p * othm::kEvalTable);
-    std::vector<Start> starts((size_t)n, Start{othp::kOpenBlack, othp::kOpenWhite, 1});
-    if (have_start)
-        for (long i = 0; i < n; i++) {
-            unsigned long long b, w;
-            int t;
-            if (fscanf(in, "%llx %llx %d", &b, &w, &t) != 3) return 2;
-            starts[(size_t)i] = Start{b, w, t};
-        }
+    if (!read_weights(in, tables) || !read_weights(in, tables + othm::kEvalTable)) return 2;
+    std::vector<Pos> starts;
+    if (have_start) {
+        read_positions(in, 0, starts, n);
+        if ((long)starts.size() != n) return 2;
+    } else {
+        starts.assign((size_t)n, Pos{othp::kOpenBlack, othp::kOpenWhite, 1, {0, 0}});
+    }
     fclose(in);
     othp::Match m;
     m.depth[0] = da;
@@ -115,7 +95,7 @@ int main(int argc, char** argv) {
     m.n_rand[0] = (u32)(ra < (int)othp::kMaxBudget ? ra : (int)othp::kMaxBudget);
     m.n_rand[1] = (u32)(rb < (int)othp::kMaxBudget ? rb : (int)othp::kMaxBudget);
     m.exact_empties = exact;
-    m.limit = limit_arg ? (u32)limit_arg : (1u << 28);
+    m.limit = node_limit(limit_arg);
     m.swap = swap != 0;
     const u64 S = othp::seed_state(seed);
     std::vector<Out> out((size_t)n);
@@ -123,8 +103,7 @@ int main(int argc, char** argv) {
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
     for (long i = 0; i < n; i++) play_one(starts[(size_t)i], othp::game_key(S, id0 + (u64)i), m, tables, order, out[(size_t)i]);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    FILE* o = fopen(argv[2], "w");
-    if (!o) return 1;
+    FILE* o = open_or_exit(argv[2], "w");
     unsigned long long nodes = 0, plies = 0;
     for (const Out& r : out) {
         fprintf(o, "%d %llx %llx %d %u %u %llu ", r.a_black, (unsigned long long)r.black, (unsigned long long)r.white,

@@ -27,6 +27,7 @@
 
 #include "../../subproc_amd/csrc/budget_core.hpp"
 #include "../../subproc_amd/csrc/play_solve_core.hpp"
+#include "host_io.hpp"
 #include "host_rules.hpp"
 
 using othm::u32;
@@ -35,19 +36,6 @@ using othm::u64;
 using SearchStack = HostStack9<othm::kFrames>;
 using SolveStack = HostStack7<oths::kFrames>;
 
-static bool read_weights(FILE* f, int8_t* w36) {
-    for (int k = 0; k < othm::kEvalPhases * othm::kEvalFeatures; k++) {
-        int v;
-        if (fscanf(f, "%d", &v) != 1 || v < -128 || v > 127) return false;
-        w36[k] = (int8_t)v;
-    }
-    return true;
-}
-
-struct Start {
-    u64 black, white;
-    int turn;
-};
 struct GameOut {
     int a_black, diff;
     u64 black, white, nodes;
@@ -73,7 +61,7 @@ static void emit(const othp::Game& G, GameOut& out) {
 
 // the first phase of game g: true = parked into `rec`, false = ended and emitted
 template <bool kOrdered, bool kBudget>
-static bool first_phase(const Start& s, u64 key, u64 g, const othp::Match& m, const othb::Budgets& bud,
+static bool first_phase(const Pos& s, u64 key, u64 g, const othp::Match& m, const othb::Budgets& bud,
                         const int* tables, GameOut& out, Record& rec) {
     memset(out.moves, 255, sizeof out.moves);
     othp::Game G;
@@ -110,15 +98,11 @@ static void second_phase(const Record& rec, u32 limit, std::vector<GameOut>& out
 }
 
 int main(int argc, char** argv) {
-    if (argc < 3) {
-        fprintf(stderr, "usage: %s ARGS OUT [order] [threads]\n", argv[0]);
-        return 2;
-    }
+    if (argc < 3) usage(argv[0], "ARGS OUT [order] [threads]");
     const int order = argc > 3 ? atoi(argv[3]) : 0;
     const int threads = argc > 4 ? atoi(argv[4]) : 16;
     if (threads < 1 || order < 0 || order > 1) return 2;
-    FILE* in = fopen(argv[1], "r");
-    if (!in) return 1;
+    FILE* in = open_or_exit(argv[1], "r");
     long n;
     unsigned long long seed, id0, limit_arg, ba, bb;
     int da, db, zone, ra, rb, swap, have_start;
@@ -129,19 +113,15 @@ int main(int argc, char** argv) {
         zone > oths::kMaxEmpties || ra < 0 || rb < 0 || limit_arg > 0xFFFFFFFFull || ba > 0xFFFFFFFFull ||
         bb > 0xFFFFFFFFull || (ba == 0) != (bb == 0))
         return 2;
-    int8_t w36[2][othm::kEvalPhases * othm::kEvalFeatures];
-    if (!read_weights(in, w36[0]) || !read_weights(in, w36[1])) return 2;
     int tables[2 * othm::kEvalTable];
-    for (int p = 0; p < 2; p++)
-        for (int e = 0; e < othm::kEvalTable; e++) othm::widen_weight(w36[p], e, tables + p * othm::kEvalTable);
-    std::vector<Start> starts((size_t)n, Start{othp::kOpenBlack, othp::kOpenWhite, 1});
-    if (have_start)
-        for (long i = 0; i < n; i++) {
-            unsigned long long b, w;
-            int t;
-            if (fscanf(in, "%llx %llx %d", &b, &w, &t) != 3) return 2;
-            starts[(size_t)i] = Start{b, w, t};
-        }
+    if (!read_weights(in, tables) || !read_weights(in, tables + othm::kEvalTable)) return 2;
+    std::vector<Pos> starts;
+    if (have_start) {
+        read_positions(in, 0, starts, n);
+        if ((long)starts.size() != n) return 2;
+    } else {
+        starts.assign((size_t)n, Pos{othp::kOpenBlack, othp::kOpenWhite, 1, {0, 0}});
+    }
     fclose(in);
     othp::Match m;
     m.depth[0] = da;
@@ -149,7 +129,7 @@ int main(int argc, char** argv) {
     m.n_rand[0] = (u32)(ra < (int)othp::kMaxBudget ? ra : (int)othp::kMaxBudget);
     m.n_rand[1] = (u32)(rb < (int)othp::kMaxBudget ? rb : (int)othp::kMaxBudget);
     m.exact_empties = zone;  // the first phase's parking line
-    m.limit = limit_arg ? (u32)limit_arg : (1u << 28);
+    m.limit = node_limit(limit_arg);
     m.swap = swap != 0;
     othb::Budgets bud;
     bud.budget[0] = (u32)ba;
@@ -162,7 +142,7 @@ int main(int argc, char** argv) {
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
     for (long i = 0; i < n; i++) {
         const u64 key = othp::game_key(S, id0 + (u64)i);
-        const Start& s = starts[(size_t)i];
+        const Pos& s = starts[(size_t)i];
         GameOut& o = out[(size_t)i];
         Record& r = slot[(size_t)i];
         bool p;
@@ -182,8 +162,7 @@ int main(int argc, char** argv) {
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
     for (long k = 0; k < parked; k++) second_phase(list[(size_t)k], m.limit, out);
     fprintf(stderr, "parked %ld of %ld\n", parked, n);
-    FILE* o = fopen(argv[2], "w");
-    if (!o) return 1;
+    FILE* o = open_or_exit(argv[2], "w");
     for (const GameOut& r : out) {
         fprintf(o, "%d %llx %llx %d %u %u %llu ", r.a_black, (unsigned long long)r.black, (unsigned long long)r.white,
                 r.diff, r.plies, r.status, (unsigned long long)r.nodes);

@@ -22,6 +22,7 @@
 
 #include "../../subproc_amd/csrc/order_core.hpp"
 #include "../../subproc_amd/csrc/search_core.hpp"
+#include "host_io.hpp"
 #include "host_rules.hpp"
 
 using othm::u32;
@@ -29,10 +30,6 @@ using othm::u64;
 
 using HostStack = HostStack9<othm::kFrames>;
 
-struct Pos {
-    u64 black, white;
-    int turn;
-};
 struct Out {
     int value;
     u32 best, status, nodes;
@@ -42,8 +39,7 @@ static Out search_one(const Pos& p, int depth, const int* table, u32 limit, int 
     if (p.black & p.white) return Out{0, othm::kNoMove, othm::kInvalid, 0};
     othm::Lane L;
     HostStack stk;
-    const bool white = p.turn == 2;
-    othm::start(L, white ? p.white : p.black, white ? p.black : p.white, depth);
+    othm::start(L, p.mover(), p.other(), depth);
     othm::Order Q;
     othm::order_reset(Q);
     if (order)
@@ -54,42 +50,24 @@ static Out search_one(const Pos& p, int depth, const int* table, u32 limit, int 
 }
 
 int main(int argc, char** argv) {
-    if (argc < 5) {
-        fprintf(stderr, "usage: %s IN OUT WEIGHTS depth [node_limit] [threads] [order]\n", argv[0]);
-        return 2;
-    }
+    if (argc < 5) usage(argv[0], "IN OUT WEIGHTS depth [node_limit] [threads] [order]");
     const int depth = atoi(argv[4]);
     const u32 limit_arg = argc > 5 ? (u32)strtoul(argv[5], nullptr, 0) : 0u;
     const int threads = argc > 6 ? atoi(argv[6]) : 16;
     const int order = argc > 7 ? atoi(argv[7]) : 0;
     if (depth < 1 || depth > othm::kMaxDepth || threads < 1 || order < 0 || order > 1) return 2;
-    const u32 limit = limit_arg ? limit_arg : (1u << 28);
-    FILE* wf = fopen(argv[3], "r");
-    if (!wf) return 1;
-    int8_t w36[othm::kEvalPhases * othm::kEvalFeatures];
-    for (int8_t& w : w36) {
-        int v;
-        if (fscanf(wf, "%d", &v) != 1 || v < -128 || v > 127) return 2;
-        w = (int8_t)v;
-    }
-    fclose(wf);
+    const u32 limit = node_limit(limit_arg);
     int table[othm::kEvalTable];
-    for (int e = 0; e < othm::kEvalTable; e++) othm::widen_weight(w36, e, table);
-    FILE* in = fopen(argv[1], "r");
-    if (!in) return 1;
+    read_weights(argv[3], table);
     std::vector<Pos> pos;
-    unsigned long long b, w;
-    int t;
-    while (fscanf(in, "%llx %llx %d", &b, &w, &t) == 3) pos.push_back(Pos{b, w, t});
-    fclose(in);
+    read_positions(argv[1], 0, pos);
     std::vector<Out> out(pos.size());
     const auto t0 = std::chrono::steady_clock::now();
     const long n = (long)pos.size();
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
     for (long i = 0; i < n; i++) out[i] = search_one(pos[i], depth, table, limit, order);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    FILE* o = fopen(argv[2], "w");
-    if (!o) return 1;
+    FILE* o = open_or_exit(argv[2], "w");
     unsigned long long nodes = 0;
     for (const Out& r : out) {
         fprintf(o, "%d %u %u %u\n", r.value, r.best, r.status, r.nodes);

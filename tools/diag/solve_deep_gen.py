@@ -10,7 +10,6 @@ and every forced-pass root of solve_cases.pool() at 13..16 empties.
     python tools/diag/solve_deep_gen.py [OUT=tests/golden/solve_deep/solve_deep.npz] [threads=16]
 """
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -19,6 +18,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
+import host_programs as hp  # noqa: E402
 import solve_cases  # noqa: E402
 import solve_ref  # noqa: E402
 
@@ -45,13 +45,10 @@ def main(argv):
     boards, turn = roots()
     with tempfile.TemporaryDirectory() as d:
         exe, inp, res = (os.path.join(d, x) for x in ("ref", "in", "out"))
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fopenmp", "-o", exe,
-                               os.path.join(ROOT, "tools", "diag", "solve_deep_ref.cpp")])
-        with open(inp, "w") as f:
-            for (b, w), t in zip(boards.tolist(), turn.tolist()):
-                f.write("%x %x %d\n" % (b, w, t))
-        subprocess.check_call([exe, inp, res, threads])
-        rows = np.array([[int(x) for x in ln.split()] for ln in open(res)], np.int64)
+        hp.build("solve_deep_ref", hp.PLAIN, exe)
+        hp.write_positions(inp, boards, turn)
+        hp.run([exe, inp, res, threads])
+        rows = hp.read_rows(res)
     assert rows.shape == (len(turn), 4)
     emp = solve_ref.empties(boards)
     for e in range(13, 17):

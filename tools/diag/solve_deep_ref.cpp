@@ -22,6 +22,9 @@
 #include <cstdlib>
 #include <vector>
 
+#define HOST_IO_NO_CORES  // the positions file's reader alone: no core header is read
+#include "host_io.hpp"
+
 typedef uint64_t u64;
 
 static const int kShift[8] = {1, 7, 8, 9, 1, 7, 8, 9};  // the first four to the left, the last four to the right
@@ -92,11 +95,6 @@ static int search(u64 P, u64 O, int alpha, int beta, bool passed, bool mobility,
     return best;
 }
 
-struct Pos {
-    u64 black, white;
-    int turn;
-};
-
 struct Job {
     int pos, kind;  // kind 0: the root ascending, 1: the root ordered, 2 + k: root move k, full window
     int value = 0;
@@ -104,22 +102,14 @@ struct Job {
 };
 
 int main(int argc, char** argv) {
-    if (argc < 3) {
-        fprintf(stderr, "usage: %s IN OUT [threads]\n", argv[0]);
-        return 2;
-    }
+    if (argc < 3) usage(argv[0], "IN OUT [threads]");
     const int threads = argc > 3 ? atoi(argv[3]) : 16;
     if (threads < 1) return 2;
-    FILE* in = fopen(argv[1], "r");
-    if (!in) return 1;
     std::vector<Pos> pos;
-    unsigned long long b, w;
-    int t;
-    while (fscanf(in, "%llx %llx %d", &b, &w, &t) == 3) pos.push_back(Pos{b, w, t});
-    fclose(in);
+    read_positions(argv[1], 0, pos);
     std::vector<Job> jobs;
     for (int i = 0; i < (int)pos.size(); i++) {
-        const u64 P = pos[i].turn == 2 ? pos[i].white : pos[i].black, O = pos[i].turn == 2 ? pos[i].black : pos[i].white;
+        const u64 P = pos[i].mover(), O = pos[i].other();
         if (P & O) return 2;
         jobs.push_back(Job{i, 0});
         jobs.push_back(Job{i, 1});
@@ -130,7 +120,7 @@ int main(int argc, char** argv) {
     for (long j = 0; j < nj; j++) {
         Job& job = jobs[j];
         const Pos& p = pos[job.pos];
-        const u64 P = p.turn == 2 ? p.white : p.black, O = p.turn == 2 ? p.black : p.white;
+        const u64 P = p.mover(), O = p.other();
         Counter c;
         if (job.kind < 2) {
             job.value = search(P, O, -65, 65, false, job.kind == 1, c);
@@ -142,11 +132,10 @@ int main(int argc, char** argv) {
         }
         job.nodes = c.nodes;
     }
-    FILE* o = fopen(argv[2], "w");
-    if (!o) return 1;
+    FILE* o = open_or_exit(argv[2], "w");
     long j = 0;
     for (int i = 0; i < (int)pos.size(); i++) {
-        const u64 P = pos[i].turn == 2 ? pos[i].white : pos[i].black, O = pos[i].turn == 2 ? pos[i].black : pos[i].white;
+        const u64 P = pos[i].mover(), O = pos[i].other();
         const Job &asc = jobs[j], &ord = jobs[j + 1];
         j += 2;
         if (asc.value != ord.value) {

@@ -36,6 +36,7 @@
 
 #include "../../subproc_amd/csrc/solve_hash_core.hpp"
 #include "../../subproc_amd/csrc/solve_tree_core.hpp"
+#include "host_io.hpp"
 #include "host_rules.hpp"
 
 using othe::Node;
@@ -81,10 +82,6 @@ struct ThreadTreeAtomics {
     static void store(u64* p, u64 v) { __atomic_store_n(p, v, __ATOMIC_RELEASE); }
 };
 
-struct Pos {
-    u64 black, white;
-    int turn;
-};
 struct Out {
     int value;
     u32 best, status;
@@ -102,8 +99,7 @@ static bool expand(const Pos& p, int max_empties, int task_empties, u32 npp, std
     }
     slab.assign(npp, Node{});
     tasks.clear();
-    const bool white = p.turn == 2;
-    othe::make_node<HostRules>(slab[0], white ? p.white : p.black, white ? p.black : p.white, -1, oths::kNoMove);
+    othe::make_node<HostRules>(slab[0], p.mover(), p.other(), -1, oths::kNoMove);
     u32 lvl[othe::kMaxRounds + 2] = {0, 1};
     u32 begin = 0, end = 1;
     int rounds = 0;
@@ -227,13 +223,10 @@ static Out solve_threads(std::vector<Node>& slab, const std::vector<u32>& tasks,
 }
 
 int main(int argc, char** argv) {
-    if (argc < 10) {
-        fprintf(stderr,
-                "usage: %s a|b IN OUT max_empties task_empties nodes_per_position order hash_bits hash_min_empties "
-                "[task_orders] [plain] [threads] [seed] [node_limit]\n",
-                argv[0]);
-        return 2;
-    }
+    if (argc < 10)
+        usage(argv[0],
+              "a|b IN OUT max_empties task_empties nodes_per_position order hash_bits hash_min_empties "
+              "[task_orders] [plain] [threads] [seed] [node_limit]");
     const char mode = argv[1][0];
     const int max_empties = atoi(argv[4]), task_empties = atoi(argv[5]);
     const long npp = atol(argv[6]);
@@ -250,21 +243,15 @@ int main(int argc, char** argv) {
         npp < othe::kMinNodes || npp > (1 << 24))
         return 2;
     if (bits < othh::kMinBits || bits > 24 || gate < othh::kMinGate || gate > othh::kMaxGate) return 2;
-    const u32 limit = limit_arg ? limit_arg : (1u << 28);
-    FILE* in = fopen(argv[2], "r");
-    if (!in) return 1;
+    const u32 limit = node_limit(limit_arg);
     std::vector<Pos> pos;
-    unsigned long long b, w;
-    int t;
-    while (fscanf(in, "%llx %llx %d", &b, &w, &t) == 3) pos.push_back(Pos{b, w, t});
-    fclose(in);
+    read_positions(argv[2], 0, pos);
     std::vector<othh::Entry> entries((size_t)1 << bits);  // all zero: empty; never cleared below
     othh::Table tab;
     tab.e = entries.data();
     tab.shift = 64 - bits;
     tab.min_empties = gate;
-    FILE* o = fopen(argv[3], "w");
-    if (!o) return 1;
+    FILE* o = open_or_exit(argv[3], "w");
     unsigned long long hashed = 0, unhashed = 0;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<Node> tree;

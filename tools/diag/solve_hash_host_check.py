@@ -16,7 +16,6 @@ orderings on the accesses, so this run checks the protocol, not the device's
 spelling of it with fences (DESIGN.md §19 argues that one).
 """
 import os
-import subprocess
 import sys
 import tempfile
 
@@ -25,26 +24,24 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
+import host_programs as hp  # noqa: E402
 import solve_cases  # noqa: E402
 
-SOURCE = os.path.join(ROOT, "tools", "diag", "solve_hash_host.cpp")
 FIXTURE = os.path.join(ROOT, "tests", "golden", "solve_deep", "solve_deep.npz")
-BUILDS = {"asan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "tsan": ["-fsanitize=thread"]}
+BUILDS = {"asan": hp.SANITIZED, "tsan": hp.THREAD_SANITIZED}
 
 
 def run(binary, mode, boards, turn, rv, rm, max_empties, task_empties, npp, order, bits, label):
     with tempfile.TemporaryDirectory() as d:
         inp, out = os.path.join(d, "in"), os.path.join(d, "out")
-        with open(inp, "w") as f:
-            for (b, w), t in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist()):
-                f.write("%x %x %d\n" % (b, w, t))
-        r = subprocess.run([binary, mode, inp, out, str(max_empties), str(task_empties), str(npp), str(order), str(bits),
-                            "1", "3", "1", "8"], capture_output=True, text=True)
-        if r.returncode != 0 or "Sanitizer" in r.stderr:
-            print(r.stderr)
-            print("%-60s FAILED (exit %d)" % (label, r.returncode))
+        hp.write_positions(inp, boards, turn)
+        try:
+            hp.run([binary, mode, inp, out, max_empties, task_empties, npp, order, bits, 1, 3, 1, 8])
+        except hp.ProgramFailed as e:  # a non-zero exit status or a sanitizer's report
+            print(e.result.stderr)
+            print("%-60s FAILED (exit %d)" % (label, e.result.returncode))
             return 1
-        rows = np.array([[int(x) for x in ln.split()] for ln in open(out)], np.int64).reshape(len(turn), -1, 4)
+        rows = hp.read_rows(out, (len(turn), -1, 4))
     ok = (rows[:, :, 2] == 1).all() and (rows[:, :, 0] == rv[:, None]).all() and (rows[:, :, 1] == rm[:, None]).all()
     print("%-60s %4d roots  nodes %s  %s" % (label, len(turn), "/".join(str(int(x)) for x in rows[:, :, 3].sum(0)),
                                            "equal" if ok else "DIFFERS"), flush=True)
@@ -65,8 +62,7 @@ def main():
     with tempfile.TemporaryDirectory() as d:
         exe = {}
         for name, flags in BUILDS.items():
-            exe[name] = os.path.join(d, "solve_hash_host_" + name)
-            subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-pthread", *flags, "-o", exe[name], SOURCE])
+            exe[name] = hp.build("solve_hash_host", flags, os.path.join(d, "solve_hash_host_" + name))
         for order in (0, 1):
             bad += run(exe["asan"], "a", *pool(3, 8), 16, 3, 64, order, 4, "asan, a, 3..8 empties, slab 64, 16 entries, order %d" % order)
             bad += run(exe["asan"], "a", *pool(6, 8), 16, 3, 65536, order, 16, "asan, a, 6..8 empties, 2^16 entries, order %d" % order)

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../subproc_amd/csrc/solve_core.hpp"
+#include "host_io.hpp"
 #include "host_rules.hpp"
 
 using oths::u32;
@@ -25,10 +26,6 @@ using oths::u64;
 
 using HostStack = HostStack7<oths::kFrames>;
 
-struct Pos {
-    u64 black, white;
-    int turn;
-};
 struct Out {
     int value;
     u32 best, status, nodes;
@@ -39,37 +36,27 @@ static Out solve_one(const Pos& p, int max_empties, u32 limit) {
     if (st != oths::kSolved) return Out{0, oths::kNoMove, st, 0};
     oths::Lane L;
     HostStack stk;
-    const bool white = p.turn == 2;
-    oths::start(L, white ? p.white : p.black, white ? p.black : p.white);
+    oths::start(L, p.mover(), p.other());
     while (L.depth >= 0) oths::advance<HostRules>(L, stk, limit);
     return Out{L.value, L.best_mv, L.status, L.nodes};
 }
 
 int main(int argc, char** argv) {
-    if (argc < 3) {
-        fprintf(stderr, "usage: %s IN OUT [max_empties] [node_limit] [threads]\n", argv[0]);
-        return 2;
-    }
+    if (argc < 3) usage(argv[0], "IN OUT [max_empties] [node_limit] [threads]");
     const int max_empties = argc > 3 ? atoi(argv[3]) : oths::kMaxEmpties;
     const u32 limit_arg = argc > 4 ? (u32)strtoul(argv[4], nullptr, 0) : 0u;
     const int threads = argc > 5 ? atoi(argv[5]) : 16;
     if (max_empties < 0 || max_empties > oths::kMaxEmpties || threads < 1) return 2;
-    const u32 limit = limit_arg ? limit_arg : (1u << 28);
-    FILE* in = fopen(argv[1], "r");
-    if (!in) return 1;
+    const u32 limit = node_limit(limit_arg);
     std::vector<Pos> pos;
-    unsigned long long b, w;
-    int t;
-    while (fscanf(in, "%llx %llx %d", &b, &w, &t) == 3) pos.push_back(Pos{b, w, t});
-    fclose(in);
+    read_positions(argv[1], 0, pos);
     std::vector<Out> out(pos.size());
     const auto t0 = std::chrono::steady_clock::now();
     const long n = (long)pos.size();
 #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
     for (long i = 0; i < n; i++) out[i] = solve_one(pos[i], max_empties, limit);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    FILE* o = fopen(argv[2], "w");
-    if (!o) return 1;
+    FILE* o = open_or_exit(argv[2], "w");
     unsigned long long nodes = 0;
     for (const Out& r : out) {
         fprintf(o, "%d %u %u %u\n", r.value, r.best, r.status, r.nodes);

@@ -29,6 +29,7 @@
 
 #include "../../subproc_amd/csrc/solve_order_core.hpp"
 #include "../../subproc_amd/csrc/solve_tree_core.hpp"
+#include "host_io.hpp"
 #include "host_rules.hpp"
 
 using othe::Node;
@@ -37,10 +38,6 @@ using othe::u64;
 
 using HostStack = HostStack7<oths::kFrames>;
 
-struct Pos {
-    u64 black, white;
-    int turn;
-};
 struct Out {
     int value;
     u32 best, status;
@@ -55,8 +52,7 @@ static Out solve_one(const Pos& p, int max_empties, int task_empties, u32 npp, u
     const u32 cls = oths::classify(p.black, p.white, 64 - HostRules::count(p.black | p.white), max_empties);
     if (cls != oths::kSolved) return Out{0, oths::kNoMove, cls, 0};
     std::vector<Node> slab(npp);
-    const bool white = p.turn == 2;
-    othe::make_node<HostRules>(slab[0], white ? p.white : p.black, white ? p.black : p.white, -1, oths::kNoMove);
+    othe::make_node<HostRules>(slab[0], p.mover(), p.other(), -1, oths::kNoMove);
     u32 lvl[othe::kMaxRounds + 2] = {0, 1};
     u32 begin = 0, end = 1;
     int rounds = 0;
@@ -134,13 +130,9 @@ static Out solve_one(const Pos& p, int max_empties, int task_empties, u32 npp, u
 }
 
 int main(int argc, char** argv) {
-    if (argc < 5) {
-        fprintf(stderr,
-                "usage: %s IN OUT max_empties task_empties [nodes_per_position] [node_limit] [seed] [order] [threads] "
-                "[task_orders]\n",
-                argv[0]);
-        return 2;
-    }
+    if (argc < 5)
+        usage(argv[0],
+              "IN OUT max_empties task_empties [nodes_per_position] [node_limit] [seed] [order] [threads] [task_orders]");
     const int max_empties = atoi(argv[3]), task_empties = atoi(argv[4]);
     const long npp = argc > 5 ? atol(argv[5]) : 65536;
     const u32 limit_arg = argc > 6 ? (u32)strtoul(argv[6], nullptr, 0) : 0u;
@@ -152,14 +144,9 @@ int main(int argc, char** argv) {
     if (max_empties < 0 || max_empties > othe::kMaxEmpties || task_empties < 1 || task_empties > oths::kMaxEmpties ||
         npp < othe::kMinNodes || npp > (1 << 24))
         return 2;
-    const u32 limit = limit_arg ? limit_arg : (1u << 28);
-    FILE* in = fopen(argv[1], "r");
-    if (!in) return 1;
+    const u32 limit = node_limit(limit_arg);
     std::vector<Pos> pos;
-    unsigned long long b, w;
-    int t;
-    while (fscanf(in, "%llx %llx %d", &b, &w, &t) == 3) pos.push_back(Pos{b, w, t});
-    fclose(in);
+    read_positions(argv[1], 0, pos);
     const long n = (long)pos.size();
     std::vector<Out> out((size_t)n * norders);
     const auto t0 = std::chrono::steady_clock::now();
@@ -169,8 +156,7 @@ int main(int argc, char** argv) {
             out[(size_t)i * norders + order] =
                 solve_one(pos[i], max_empties, task_empties, (u32)npp, limit, (Order)order, seed, ordered);
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    FILE* o = fopen(argv[2], "w");
-    if (!o) return 1;
+    FILE* o = open_or_exit(argv[2], "w");
     unsigned long long nodes = 0;
     for (long i = 0; i < n; i++)
         for (int order = 0; order < norders; order++) {

@@ -16,7 +16,6 @@ quick: the fixture's 13-empties roots only, at task_empties 10 (what a
 sanitizer build gets through in a few minutes).
 """
 import os
-import subprocess
 import sys
 import tempfile
 import time
@@ -26,6 +25,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
+import host_programs as hp  # noqa: E402
 import solve_cases  # noqa: E402
 
 SOLVED, NOROOM = 1, 4
@@ -39,13 +39,9 @@ def run(binary, boards, turn, max_empties, task_empties, npp=DEFAULT_NODES, node
     """(value, move, status, nodes), each [task_orders][n]."""
     with tempfile.TemporaryDirectory() as d:
         inp, out = os.path.join(d, "in"), os.path.join(d, "out")
-        with open(inp, "w") as f:
-            for (b, w), t in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist()):
-                f.write("%x %x %d\n" % (b, w, t))
-        subprocess.run([binary, inp, out, str(max_empties), str(task_empties), str(npp), str(node_limit), str(seed),
-                        str(order), str(threads), str(task_orders)], check=True, stderr=subprocess.DEVNULL)
-        rows = np.array([[int(x) for x in ln.split()] for ln in open(out)], np.int64).reshape(-1, task_orders, 4)
-    return tuple(rows[:, :, k].T for k in range(4))
+        hp.write_positions(inp, boards, turn)
+        hp.run([binary, inp, out, max_empties, task_empties, npp, node_limit, seed, order, threads, task_orders])
+        return hp.read_rows(out, orders=task_orders)
 
 
 def compare(label, got, rv, rm, allow_noroom=False):

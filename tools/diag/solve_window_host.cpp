@@ -37,6 +37,7 @@
 
 #include "../../subproc_amd/csrc/solve_hash_core.hpp"
 #include "../../subproc_amd/csrc/solve_tree_core.hpp"
+#include "host_io.hpp"
 #include "host_rules.hpp"
 
 using othe::Node;
@@ -65,10 +66,9 @@ struct ThreadTreeAtomics {
     static void store(u64* p, u64 v) { __atomic_store_n(p, v, __ATOMIC_RELEASE); }
 };
 
-struct Pos {
-    u64 black, white;
-    int turn, alpha, beta;
-};
+// the line's window: its two extra columns
+static int alpha_of(const Pos& p) { return (int)p.extra[0]; }
+static int beta_of(const Pos& p) { return (int)p.extra[1]; }
 struct Out {
     int value;
     u32 best, status;
@@ -87,8 +87,7 @@ static Out solve_lane(const Pos& p, int max_empties, u32 limit, int ra, int rb) 
     if (cls != oths::kSolved) return Out{0, oths::kNoMove, cls, 0};
     oths::Lane L;
     HostStack stk;
-    const bool white = p.turn == 2;
-    oths::start(L, white ? p.white : p.black, white ? p.black : p.white, ra, rb);
+    oths::start(L, p.mover(), p.other(), ra, rb);
     while (L.depth >= 0) oths::advance<HostRules>(L, stk, limit);
     if (L.status == oths::kSolved) L.value = oths::clamp_to_window(L.value, ra, rb);
     return Out{L.value, L.best_mv, L.status, L.nodes};
@@ -105,8 +104,7 @@ static bool expand(const Pos& p, int max_empties, int task_empties, u32 npp, int
     }
     if (slab.size() != npp) slab.assign(npp, Node{});  // (every node used below is made whole first)
     tasks.clear();
-    const bool white = p.turn == 2;
-    othe::make_node<HostRules>(slab[0], white ? p.white : p.black, white ? p.black : p.white, -1, oths::kNoMove);
+    othe::make_node<HostRules>(slab[0], p.mover(), p.other(), -1, oths::kNoMove);
     u32 lvl[othe::kMaxRounds + 2] = {0, 1};
     u32 begin = 0, end = 1;
     int rounds = 0;
@@ -248,22 +246,16 @@ int main(int argc, char** argv) {
     if (max_empties < 0 || max_empties > othe::kMaxEmpties || task_empties < 1 || task_empties > oths::kMaxEmpties ||
         npp < othe::kMinNodes || npp > (1 << 24))
         return 2;
-    FILE* in = fopen(argv[2], "r");
-    if (!in) return 1;
     std::vector<Pos> pos;
-    unsigned long long b, w;
-    int t, lo, hi;
-    while (fscanf(in, "%llx %llx %d %d %d", &b, &w, &t, &lo, &hi) == 5) pos.push_back(Pos{b, w, t, lo, hi});
-    fclose(in);
-    FILE* o = fopen(argv[3], "w");
-    if (!o) return 1;
+    read_positions(argv[2], 2, pos);
+    FILE* o = open_or_exit(argv[3], "w");
     std::vector<Node> tree;
     std::vector<u32> tasks;
     if (mode == 'a') {
         const int threads = argc > 7 ? atoi(argv[7]) : 1;
         const u32 seed = argc > 8 ? (u32)strtoul(argv[8], nullptr, 0) : 7u;
         const u32 limit_arg = argc > 9 ? (u32)strtoul(argv[9], nullptr, 0) : 0u;
-        const u32 limit = limit_arg ? limit_arg : (1u << 28);
+        const u32 limit = node_limit(limit_arg);
         if (threads < 1 || threads > 64) return 2;
         const long n = (long)pos.size();
         std::vector<Out> res((size_t)n * 10);  // the lane, the lane under the full window, the eight split runs
@@ -272,14 +264,14 @@ int main(int argc, char** argv) {
             const Pos& p = pos[i];
             // (the one-lane machine takes 12 empties at most: above, its columns are a skipped position's)
             const int lane_empties = std::min(max_empties, oths::kMaxEmpties);
-            res[i * 10] = solve_lane(p, lane_empties, limit, p.alpha, p.beta);
+            res[i * 10] = solve_lane(p, lane_empties, limit, alpha_of(p), beta_of(p));
             res[i * 10 + 1] = solve_lane(p, lane_empties, limit, -oths::kInf, oths::kInf);
             Out first;
-            const bool run = expand(p, max_empties, task_empties, (u32)npp, p.alpha, p.beta, tree, tasks, first);
+            const bool run = expand(p, max_empties, task_empties, (u32)npp, alpha_of(p), beta_of(p), tree, tasks, first);
             for (int ordered = 0; ordered < 2; ordered++)
                 for (int order = 0; order < 4; order++)
                     res[i * 10 + 2 + ordered * 4 + order] =
-                        run ? solve_serial(tree, tasks, first, (Order)order, seed, p.alpha, p.beta, ordered, limit) : first;
+                        run ? solve_serial(tree, tasks, first, (Order)order, seed, alpha_of(p), beta_of(p), ordered, limit) : first;
         }
         for (long i = 0; i < n; i++) {
             const Out &one = res[i * 10], &full = res[i * 10 + 1];
@@ -294,7 +286,7 @@ int main(int argc, char** argv) {
     const int ordered = atoi(argv[7]), bits = atoi(argv[8]), gate = atoi(argv[9]), phase = atoi(argv[10]);
     const int threads = argc > 11 ? atoi(argv[11]) : 8;
     const u32 limit_arg = argc > 12 ? (u32)strtoul(argv[12], nullptr, 0) : 0u;
-    const u32 limit = limit_arg ? limit_arg : (1u << 28);
+    const u32 limit = node_limit(limit_arg);
     if (ordered < 0 || ordered > 1 || phase < 0 || phase > 1 || threads < 1 || threads > 64) return 2;
     if (bits < othh::kMinBits || bits > 24 || gate < othh::kMinGate || gate > othh::kMaxGate) return 2;
     std::vector<othh::Entry> entries((size_t)1 << bits);  // all zero: empty; never cleared below
@@ -306,7 +298,7 @@ int main(int argc, char** argv) {
     for (int pass = 0; pass < 2; pass++) {
         const bool full = (pass == 0) == (phase == 0);
         for (size_t i = 0; i < pos.size(); i++) {
-            const int ra = full ? -othe::kInf : pos[i].alpha, rb = full ? othe::kInf : pos[i].beta;
+            const int ra = full ? -othe::kInf : alpha_of(pos[i]), rb = full ? othe::kInf : beta_of(pos[i]);
             Out first;
             const bool run = expand(pos[i], max_empties, task_empties, (u32)npp, ra, rb, tree, tasks, first);
             res[i * 2 + (full ? 1 : 0)] = run ? solve_threads(tree, tasks, first, threads, ra, rb, &tab, ordered, limit) : first;

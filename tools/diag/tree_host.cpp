@@ -26,6 +26,7 @@
 
 #include "../../subproc_amd/csrc/order_core.hpp"
 #include "../../subproc_amd/csrc/tree_core.hpp"
+#include "host_io.hpp"
 #include "host_rules.hpp"
 
 using otht::Node;
@@ -34,10 +35,6 @@ using otht::u64;
 
 using HostStack = HostStack9<othm::kFrames>;
 
-struct Pos {
-    u64 black, white;
-    int turn;
-};
 struct Out {
     int value;
     u32 best, status;
@@ -51,9 +48,7 @@ static Out search_one(const Pos& p, int depth, int split, u32 npp, const int* ta
                       u32 seed, int ordered) {
     if (p.black & p.white) return Out{0, othm::kNoMove, othm::kInvalid, 0};
     std::vector<Node> slab(npp);
-    const bool white = p.turn == 2;
-    otht::make_node<HostRules>(slab[0], white ? p.white : p.black, white ? p.black : p.white, -1, othm::kNoMove, depth,
-                               otht::kSideRoot);
+    otht::make_node<HostRules>(slab[0], p.mover(), p.other(), -1, othm::kNoMove, depth, otht::kSideRoot);
     const int target = depth - split;
     u32 lvl[otht::kMaxRounds + 2] = {0, 1};
     u32 begin = 0, end = 1;
@@ -131,10 +126,7 @@ static Out search_one(const Pos& p, int depth, int split, u32 npp, const int* ta
 }
 
 int main(int argc, char** argv) {
-    if (argc < 6) {
-        fprintf(stderr, "usage: %s IN OUT WEIGHTS depth split [nodes_per_position] [node_limit] [seed] [order]\n", argv[0]);
-        return 2;
-    }
+    if (argc < 6) usage(argv[0], "IN OUT WEIGHTS depth split [nodes_per_position] [node_limit] [seed] [order]");
     const int depth = atoi(argv[4]), split = atoi(argv[5]);
     const long npp = argc > 6 ? atol(argv[6]) : 32768;
     const u32 limit_arg = argc > 7 ? (u32)strtoul(argv[7], nullptr, 0) : 0u;
@@ -144,27 +136,12 @@ int main(int argc, char** argv) {
     if (split < 1 || split > otht::kMaxSplit || depth <= split || depth > split + othm::kMaxDepth ||
         npp < otht::kMinNodes || npp > (1 << 24))
         return 2;
-    const u32 limit = limit_arg ? limit_arg : (1u << 28);
-    FILE* wf = fopen(argv[3], "r");
-    if (!wf) return 1;
-    int8_t w36[othm::kEvalPhases * othm::kEvalFeatures];
-    for (int8_t& w : w36) {
-        int v;
-        if (fscanf(wf, "%d", &v) != 1 || v < -128 || v > 127) return 2;
-        w = (int8_t)v;
-    }
-    fclose(wf);
+    const u32 limit = node_limit(limit_arg);
     int table[othm::kEvalTable];
-    for (int e = 0; e < othm::kEvalTable; e++) othm::widen_weight(w36, e, table);
-    FILE* in = fopen(argv[1], "r");
-    if (!in) return 1;
+    read_weights(argv[3], table);
     std::vector<Pos> pos;
-    unsigned long long b, w;
-    int t;
-    while (fscanf(in, "%llx %llx %d", &b, &w, &t) == 3) pos.push_back(Pos{b, w, t});
-    fclose(in);
-    FILE* o = fopen(argv[2], "w");
-    if (!o) return 1;
+    read_positions(argv[1], 0, pos);
+    FILE* o = open_or_exit(argv[2], "w");
     for (const Pos& p : pos) {
         for (int order = 0; order < 4; order++) {
             const Out r = search_one(p, depth, split, (u32)npp, table, limit, (Order)order, seed, ordered);

@@ -10,7 +10,6 @@ tree_core.hpp.
     python tools/diag/tree_host_check.py [BINARY=tools/diag/tree_host_asan] [case ...]
 """
 import os
-import subprocess
 import sys
 import tempfile
 import time
@@ -20,6 +19,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
+import host_programs as hp  # noqa: E402
 import search_ref  # noqa: E402
 import solve_cases  # noqa: E402
 import tree_cases  # noqa: E402
@@ -32,14 +32,10 @@ def run(binary, boards, turn, weights, depth, split, npp=32768, node_limit=1 << 
     """(value, move, status, nodes), each [4 orders][n]."""
     with tempfile.TemporaryDirectory() as d:
         inp, out, wf = (os.path.join(d, x) for x in ("in", "out", "w"))
-        with open(inp, "w") as f:
-            for (b, w), t in zip(np.asarray(boards, np.uint64).tolist(), np.asarray(turn).tolist()):
-                f.write("%x %x %d\n" % (b, w, t))
-        with open(wf, "w") as f:
-            f.write(" ".join(str(int(x)) for x in np.asarray(weights).reshape(-1)) + "\n")
-        subprocess.run([binary, inp, out, wf, str(depth), str(split), str(npp), str(node_limit), str(seed)], check=True)
-        rows = np.array([[int(x) for x in ln.split()] for ln in open(out)], np.int64).reshape(-1, 4, 4)
-    return tuple(rows[:, :, k].T for k in range(4))
+        hp.write_positions(inp, boards, turn)
+        hp.write_weights(wf, weights, end="\n")
+        sys.stderr.write(hp.run([binary, inp, out, wf, depth, split, npp, node_limit, seed]).stderr)
+        return hp.read_rows(out, orders=4)
 
 
 def compare(label, got, rv, rm, allow_noroom=False):
