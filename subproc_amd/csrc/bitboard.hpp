@@ -39,13 +39,27 @@ constexpr u64 INNER_FILES = 0x7E7E7E7E7E7E7E7Eull;  // files b..g: a disc on a/h
 // function's value on (a, b, c) = (0xF0, 0xCC, 0xAA): 0xCA = a ? b : c,
 // 0x80 = a & b & c, 0xFE = a | b | c, 0x30 = a & ~b, 0x20 = a & ~b & c,
 // 0x04 = ~a & b & ~c.
-template <int TT>
+template <int TT, bool LO_FIRST = false>
 __device__ __forceinline__ u64 bitop3(u64 a, u64 b, u64 c) {
     // (the builtin returns int: take both halves as u32, no sign extension)
-    const u32 hi = (u32)__builtin_amdgcn_bitop3_b32((u32)(a >> 32), (u32)(b >> 32), (u32)(c >> 32), TT);
-    const u32 lo = (u32)__builtin_amdgcn_bitop3_b32((u32)a, (u32)b, (u32)c, TT);
+    u32 hi, lo;
+    if (LO_FIRST) {
+        lo = (u32)__builtin_amdgcn_bitop3_b32((u32)a, (u32)b, (u32)c, TT);
+        hi = (u32)__builtin_amdgcn_bitop3_b32((u32)(a >> 32), (u32)(b >> 32), (u32)(c >> 32), TT);
+    } else {
+        hi = (u32)__builtin_amdgcn_bitop3_b32((u32)(a >> 32), (u32)(b >> 32), (u32)(c >> 32), TT);
+        lo = (u32)__builtin_amdgcn_bitop3_b32((u32)a, (u32)b, (u32)c, TT);
+    }
     return ((u64)hi << 32) | lo;
 }
+// LAY: knobs that change no arithmetic, only what hipcc's scheduler and register
+// allocator see (analyse, flips_col; a template parameter next to ORDER, 0 = the
+// form every kernel but the random rollout keeps).  A v_bitop3_b32 whose three
+// sources sit in one VGPR bank issues in 4.3 cycles instead of 2.5; which ones
+// do is an accident of the allocation, and these knobs re-roll it
+// (tools/valu_mix.py counts; the table is at kRandomLay in othello.hip).
+constexpr int kLayBarMid = 1;        // a scheduling barrier between the two fills of a direction pair
+constexpr int kLayLoFirstFlips = 2;  // run_prefix takes the low half of its two bitop3 first
 // The three-input logic of these kernels goes through v_bitop3_b32 by hand:
 // measured on the box (tools/diag/valu_rate5.cpp, 8 waves/SIMD) it issues in
 // 2.4-2.5 cycles per wave-instruction where v_bfi_b32 and v_or3_b32 take 4.2,
@@ -70,6 +84,20 @@ __device__ __forceinline__ u32 sh32(u32 x) {
     u32 r;
     if (L) asm("v_lshlrev_b32_e64 %0, %2, %1" : "=v"(r) : "v"(x), "i"(K));
     else asm("v_lshrrev_b32_e64 %0, %2, %1" : "=v"(r) : "v"(x), "i"(K));
+    return r;
+}
+// a 32-bit add of a constant and a copy in their VOP3 encodings (the random
+// loop's pass bookkeeping: hipcc's v_add_u32_e32 / v_mov_b32_e32 are VOP2 / VOP1)
+template <int K>
+__device__ __forceinline__ u32 add32(u32 x) {
+    static_assert(K >= -16 && K <= 64, "an inline constant");
+    u32 r;
+    asm("v_add_u32_e64 %0, %1, %2" : "=v"(r) : "v"(x), "i"(K));
+    return r;
+}
+__device__ __forceinline__ u32 mov32(u32 x) {
+    u32 r;
+    asm("v_mov_b32_e64 %0, %1" : "=v"(r) : "v"(x));
     return r;
 }
 // 64-bit shifts as single v_lshlrev_b64 / v_lshrrev_b64 (inline asm): with
@@ -215,8 +243,10 @@ __device__ __forceinline__ u64 fill_reach(u64 P, const PairProp& q, u64& m) {
 // folded into the fills: 7-8-9 leaves the fewest in the random loop (14 per
 // two plies; 28-34 at the others), the greedy child loop (6; 8-10) and the
 // eval child loop (17; 19-21), and the least scratch in the 1-ply kernels.
+// (The random loop has since picked its own order together with LAY:
+// kRandomFillOrder in othello.hip.)
 constexpr int kFillOrder = 789;
-template <int ORDER = kFillOrder>
+template <int ORDER = kFillOrder, int LAY = 0>
 __device__ __forceinline__ void analyse(u64 P, u64 O, Position& s) {
     const u64 Oi = and2(O, INNER_FILES);
     s.Oi = Oi;
@@ -245,14 +275,17 @@ __device__ __forceinline__ void analyse(u64 P, u64 O, Position& s) {
             if (order[k] == 8) {
                 const PairProp v = pair_prop<8>(O);
                 s.G[2] = fill_reach<8, true>(P, v, m);
+                if (LAY & kLayBarMid) __builtin_amdgcn_sched_barrier(0);
                 s.G[3] = fill_reach<8, false>(P, v, m);
             } else if (order[k] == 9) {
                 const PairProp d9 = pair_prop<9>(Oi);
                 s.G[4] = fill_reach<9, true>(P, d9, m);
+                if (LAY & kLayBarMid) __builtin_amdgcn_sched_barrier(0);
                 s.G[5] = fill_reach<9, false>(P, d9, m);
             } else {
                 const PairProp d7 = pair_prop<7>(Oi);
                 s.G[6] = fill_reach<7, true>(P, d7, m);
+                if (LAY & kLayBarMid) __builtin_amdgcn_sched_barrier(0);
                 s.G[7] = fill_reach<7, false>(P, d7, m);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -314,9 +347,11 @@ __device__ __forceinline__ u64 and3(u64 a, u64 b, u64 c) { return bitop3<0x80>(a
 // lie in G, hence in P).  place() ORs the flips into the mover's discs and
 // clears them from the opponent's, so own discs among them change neither
 // board; whoever counts or publishes flips must mask them with O first.
+template <int LAY = 0>
 __device__ __forceinline__ u64 run_prefix(u64 R, u64 G, u64 P) {
-    const u64 x = bitop3<0xB0>(R, G, P);  // R & (~G | P)
-    return and3(R, G, dec64(x));
+    constexpr bool lf = (LAY & kLayLoFirstFlips) != 0;
+    const u64 x = bitop3<0xB0, lf>(R, G, P);  // R & (~G | P)
+    return bitop3<0x80, lf>(R, G, dec64(x));
 }
 
 // The run sets flips_col reads, in the orientation it reads them: the runs
@@ -367,15 +402,16 @@ struct Flips {
     u64 f, fr;
 };
 // col = tab + sq: the move's column of the table (rows 64 entries apart)
+template <int LAY = 0>
 __device__ __forceinline__ Flips flips_col(u64 mv, const RunSets& s, const u64* col) {
     const Runs& r = s.r;
     const u64 rmv = col[(kRayRows + 1) * 64];
     u64 f = bitop3<0xBA>(r.A1, lshl1_add(mv, r.A1), mv);     // (A1 & ~(A1 + (mv << 1))) | mv
     u64 fr = bitop3<0xBA>(r.rA0, lshl1_add(rmv, r.rA0), rmv);  // west, in reversed space
-    f = or3(f, run_prefix(col[0 * 64], r.G3, s.P), run_prefix(col[1 * 64], r.G5, s.P));
-    f = or2(f, run_prefix(col[2 * 64], r.G7, s.P));
-    fr = or3(fr, run_prefix(col[3 * 64], r.rG2, s.rP), run_prefix(col[4 * 64], r.rG4, s.rP));
-    fr = or2(fr, run_prefix(col[5 * 64], r.rG6, s.rP));
+    f = or3(f, run_prefix<LAY>(col[0 * 64], r.G3, s.P), run_prefix<LAY>(col[1 * 64], r.G5, s.P));
+    f = or2(f, run_prefix<LAY>(col[2 * 64], r.G7, s.P));
+    fr = or3(fr, run_prefix<LAY>(col[3 * 64], r.rG2, s.rP), run_prefix<LAY>(col[4 * 64], r.rG4, s.rP));
+    fr = or2(fr, run_prefix<LAY>(col[5 * 64], r.rG6, s.rP));
     return Flips{f, rev64(fr)};
 }
 __device__ __forceinline__ Flips flips_rays(u32 sq, const RunSets& r, const u64* tab) {
@@ -507,10 +543,11 @@ __device__ __forceinline__ u32 add_lshl3(u32 a, u32 b) {
 // c_lo = __popc((u32)x), which the caller has from counting x (popcount_lo).
 // Returns 8 x the square: the byte offset of the square's entries in the LDS
 // ray table.  Each level keeps k as k or k - c by the subtraction's borrow
-// (kth_level; formerly min(k, k - c)), the byte is one v_bfe_u32 at the last
-// level's offset, and the three level offsets are disjoint bits (32 | 16 | 8):
-// one v_or3 and one v_add_lshl with the table entry give the offset
-// (31 -> 24 VALU per pick with the address arithmetic).
+// (kth_level; formerly min(k, k - c)), the three level offsets are disjoint
+// bits (32 | 16 | 8) ORed by one v_bitop3_b32, the byte is one v_bfe_u32 of the
+// selected word at that OR (bfe8: the word itself is never shifted), and one
+// v_add_lshl with the table entry gives the offset (31 -> 22 VALU per pick
+// with the address arithmetic).
 // One bisection level in VOP3 with the borrow as the select: b = (k < c) from
 // v_sub_co_u32's borrow, k = b ? k : k - c and off = b ? 0 : S by two
 // v_cndmask_b32_e64, where min(k, k - c) cost a v_min_u32 (a slow
@@ -542,15 +579,24 @@ __device__ __forceinline__ void kth_level(u32& k, u32 c, u32& off, u32& w, u32 w
     off = o;
     if (W) w = w2;
 }
+// the byte of w at bit (off & 31): one v_bfe_u32 (the hardware takes bits 4:0 of the offset)
+__device__ __forceinline__ u32 bfe8(u32 w, u32 off) {
+    u32 r;
+    asm("v_bfe_u32 %0, %1, %2, 8" : "=v"(r) : "v"(w), "v"(off));
+    return r;
+}
 __device__ __forceinline__ u32 kth_bit_off(u64 x, u32 k, u32 c_lo, const uint8_t* tab) {
     u32 w = (u32)x, b32, s16, s8;
     kth_level<32, true>(k, c_lo, b32, w, (u32)(x >> 32));
-    kth_level<16, false>(k, __popc(w & 0xFFFFu), s16, w, 0u);
-    w >>= s16;
-    kth_level<8, false>(k, __popc(w & 0xFFu), s8, w, 0u);
-    const u32 byte = __builtin_amdgcn_ubfe(w, s8, 8);
+    // (w & 0xFFFF as a v_bitop3_b32 on a scalar constant: hipcc's v_and_b32_e32 is a
+    // VOP2 fast instruction, ~0.75 cycles dearer among the slow VOP3 ones)
+    kth_level<16, false>(k, __popc((u32)__builtin_amdgcn_bitop3_b32(w, 0xFFFFu, 0xFFFFu, 0xC0)), s16, w, 0u);
+    kth_level<8, false>(k, __popc(bfe8(w, s16)), s8, w, 0u);
     // the disjoint level offsets ORed by one v_bitop3_b32 (hipcc's v_or3_b32 is slow)
     const u32 lvl = (u32)__builtin_amdgcn_bitop3_b32(b32, s16, s8, 0xFE);
+    // the byte sits at bit s16 | s8 of w: v_bfe_u32 reads bits 4:0 of its offset,
+    // so lvl itself serves (its bit 5 is the word select), and w is never shifted
+    const u32 byte = bfe8(w, lvl);
     return add_lshl3(lvl, tab[byte * 8u + k]);
 }
 __device__ __forceinline__ u32 kth_bit_tab(u64 x, u32 k, u32 c_lo, const uint8_t* tab) {

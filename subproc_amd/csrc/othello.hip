@@ -602,9 +602,22 @@ constexpr size_t rec_stage_bytes(int policy, bool record) {
     return record && policy == OTH_POLICY_RANDOM ? (size_t)(kBlock / 64) * kRecWaveBytes : 0;
 }
 
-// the random loop's fill order (bitboard.hpp analyse): with the VOP3 logic,
-// 7-8-9 leaves the fewest same-bank v_bitop3_b32 in its loop (tools/valu_mix.py)
-constexpr int kRandomFillOrder = 789;
+// the random loop's fill order and layout knobs (bitboard.hpp analyse, LAY):
+// picked by tools/valu_mix.py for the fewest same-bank v_bitop3_b32 in the
+// two-ply loop.  Conflicts per two plies, fill order by LAY (0 = neither,
+// 1 = kLayBarMid, 2 = kLayLoFirstFlips, 3 = both):
+//   order   0   1   2   3
+//   789    14  24  14  24
+//   798    34  18  32  18
+//   879    34  38  32  36
+//   897    28   6  26   4   <- shipped (78 VGPRs; 85 is six waves per SIMD)
+//   978    38  16  34  12
+//   987    32  12  30  12
+// (Without the knobs the loop had 14 at 7-8-9.)  The allocation is an accident of
+// everything in the loop: after a change to it, run the tool over this table
+// again.  The greedy and eval kernels keep analyse's defaults.
+constexpr int kRandomFillOrder = 897;
+constexpr int kRandomLay = kLayBarMid | kLayLoFirstFlips;
 // occupancy floor of the rollout kernels (launch bounds): random and eval
 // >= 4 waves/SIMD (<= 128 VGPRs); greedy 5 (<= 96 VGPRs; hipcc spills 13
 // per-batch registers, none in the child loop): with the record change above,
@@ -723,6 +736,14 @@ __global__ __launch_bounds__(kBlock, rollout_waves_per_simd(POLICY)) void rollou
             bool b0 = side == OTH_BLACK;
             u32 discs0 = RECORD ? 0u : (u32)__popcll(P | O);
             u32 npass = 0;  // passes (RECORD: every ply)
+            // the pass flag as a disc count: a pass notes the board's discs, and
+            // the mover "has just been passed to" while that is still the count
+            // (every placement adds a disc).  A flag cleared by every placement
+            // was carried round the loop in a VGPR and turned into a lane mask
+            // and back each iteration (3 VALU per two plies); this is touched
+            // on the pass path only.  No count equals kNoPass.
+            constexpr u32 kNoPass = ~0u;
+            u32 pass_discs = kNoPass;
             if (kPool && from_pool) {  // the top (up to) 64 parked games
                 const u32 take = min(parked, 64u);
                 active = (u32)lane < take;
@@ -734,7 +755,7 @@ __global__ __launch_bounds__(kBlock, rollout_waves_per_simd(POLICY)) void rollou
                     rng.inc = e.inc;
                     g = e.g;
                     b0 = e.bits & 1u;
-                    passed = (e.bits >> 1) & 1u;
+                    pass_discs = (e.bits >> 1) & 1u ? (u32)__popcll(P | O) : kNoPass;
                     discs0 = (e.bits >> 2) & 0x7fu;
                     npass = e.bits >> 9;
                 }
@@ -779,7 +800,7 @@ __global__ __launch_bounds__(kBlock, rollout_waves_per_simd(POLICY)) void rollou
             // ended, ~7 times per batch.
             auto ply_of = [&](u64& X, u64& Y) -> bool {
                 Position pos;
-                analyse<kRandomFillOrder>(X, Y, pos);
+                analyse<kRandomFillOrder, kRandomLay>(X, Y, pos);
                 const u64 legal = pos.legal;
                 // the move count serves the zero test and the pick
                 const u32 c_lo = __popc((u32)legal), nl = c_lo + __popc((u32)(legal >> 32));
@@ -787,22 +808,22 @@ __global__ __launch_bounds__(kBlock, rollout_waves_per_simd(POLICY)) void rollou
                     // a full board is terminal at once: the other side has no
                     // empty square either, so the hand-over iteration (a
                     // second analysis) is skipped; 65% of random games end so
-                    if (passed || (X | Y) == ~0ull) {
-                        // terminal: both sides without a legal move (board.py:57-58);
-                        // a pass handed over just before is not an env-step
-                        if (passed) npass--;
-                        return true;
-                    }
+                    // terminal: both sides without a legal move (board.py:57-58).
+                    // A pass handed over just before is not an env-step: it is
+                    // taken off the count after the loop, where pass_discs
+                    // still equals the final board's discs (a full board is
+                    // never passed to: its pass would have been terminal)
+                    const u32 discs = (u32)__popcll(or2(X, Y));
+                    if (pass_discs == discs || discs == 64u) return true;
                     // the mover must pass ('PS'): hand the move over
                     if (RECORD) rec_put(npass, OTH_PASS);
-                    passed = true;
-                    npass++;
+                    pass_discs = mov32(discs);
+                    npass = add32<1>(npass);
                     return false;
                 }
-                passed = false;
                 const u32 off = kth_bit_off(legal, rng.pick(nl), c_lo, kth_tab);
                 const u64* col = ray_col(rays, off);
-                const Flips f = flips_col(col[kRayRows * 64], run_sets(X, pos), col);
+                const Flips f = flips_col<kRandomLay>(col[kRayRows * 64], run_sets(X, pos), col);
                 if (RECORD) {
                     rec_put(npass, (uint8_t)(off >> 3));
                     npass++;
@@ -819,8 +840,9 @@ __global__ __launch_bounds__(kBlock, rollout_waves_per_simd(POLICY)) void rollou
                         if ((u32)__popcll(live) <= hand_k) {
                             const u32 rank = __builtin_amdgcn_mbcnt_hi((u32)(live >> 32),
                                                                        __builtin_amdgcn_mbcnt_lo((u32)live, 0u));
+                            const u32 passed = pass_discs == (u32)__popcll(or2(P, O));
                             pool[parked0 + rank] = Parked{P, O, rng.state, rng.inc, (u32)g,
-                                                          (u32)b0 | (u32)passed << 1 | discs0 << 2 | npass << 9};
+                                                          (u32)b0 | passed << 1 | discs0 << 2 | npass << 9};
                             g = kParkedGame;
                             break;
                         }
@@ -833,7 +855,9 @@ __global__ __launch_bounds__(kBlock, rollout_waves_per_simd(POLICY)) void rollou
                 if (g == kParkedGame) active = false;
             }
             if (active) {
-                const u32 ply = RECORD ? npass : (u32)__popcll(P | O) - discs0 + npass;
+                const u32 discs = (u32)__popcll(P | O);
+                if (pass_discs == discs) npass--;  // the game ended on a pass handed over
+                const u32 ply = RECORD ? npass : discs - discs0 + npass;
                 if (RECORD) rec_put(ply, 0xFF);
                 const u64 bl = b0 ? P : O, wh = b0 ? O : P;
                 const int d = __popcll(bl) - __popcll(wh);

@@ -30,7 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # wave-instruction; v_bitop3_b32 at 2.5 -- 4.3 when its three source registers
 # are distinct and in one VGPR bank (bank = number mod 4); every shift,
 # min/max, compare, carry, select, popcount and 64-bit op at 4.0-4.4.
-FAST = re.compile(r"^v_((and|or|xor|not|mov)_b32|(add|sub)_u32|(lshlrev|lshrrev)_b16|(add|sub|min)_u16|mul_lo_u16)(_e32)?$")
+FAST = re.compile(r"^v_((and|or|xor|not|mov)_b32|(add|sub)_u32|(lshlrev|lshrrev)_b16|(add|sub|min)_u16|mul_lo_u16)(_e32|_e64)?$")
 FAST_CYC, SLOW_CYC = 2.2, 4.2
 BITOP3_CYC, BITOP3_CONFLICT_CYC = 2.5, 4.3
 MEASURED = {"v_lshlrev_b64": 4.25, "v_lshrrev_b64": 4.22, "v_lshl_add_u64": 4.24, "v_bfrev_b32_e32": 4.13,
