@@ -24,6 +24,7 @@ PLAY_SOLVE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_pla
 PERFT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_perft.h")
 MCTS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_mcts.h")
 MCTS_TREE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_mcts_tree.h")
+MCTS_WIDE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "othello_mcts_wide.h")
 
 OTH_OK = 0
 OTH_EINVAL = -1000
@@ -81,6 +82,7 @@ MCTS_MAX_BLOCKS, MCTS_NODE_BYTES, MCTS_PATH_ENTRIES, MCTS_LDS_BYTES = 4096, 32, 
 MCTS_SEARCHED, MCTS_INVALID, MCTS_NO_MOVE = 1, 2, 255
 MCTS_TREE_RECORD_BYTES, MCTS_TREE_LDS_BYTES = 32, 6672  # include/othello_mcts_tree.h
 MCTS_TREE_READY, MCTS_TREE_INVALID, MCTS_TREE_BADMOVE, MCTS_TREE_KEEP = 1, 2, 8, 255
+MCTS_WIDE_MAX_LEAVES, MCTS_WIDE_MAX_BLOCKS, MCTS_WIDE_LDS_BYTES = 16, 1024, 14912  # include/othello_mcts_wide.h
 
 # name -> (restype, argtypes); must match include/othello.h exactly
 _P, _I64, _U64, _I = ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int
@@ -257,6 +259,15 @@ MCTS_TREE_SIGNATURES = {
     "othr_advance": (_I, [_P, _I, _I, _P, *_TREES]),
 }
 
+# the wide Monte Carlo tree search, include/othello_mcts_wide.h (its own prefix likewise): othu_mcts's arguments with
+# `leaves` after `iterations`
+MCTS_WIDE_SIGNATURES = {
+    "othv_mcts_wide": (_I, [_P, _P, _I, _I, ctypes.c_float, _P, _U64, _U64, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                            _I64, _I64, _P]),
+    "othv_mcts_wide_scratch_bytes": (_I64, [_I64, _I, _I]),
+    "othv_mcts_wide_grid": (_I, [_I64, _I]),
+}
+
 
 class OthelloLibraryError(RuntimeError):
     pass
@@ -291,7 +302,8 @@ def load():
                               **TREE_SIGNATURES, **ORDER_SIGNATURES, **SOLVE_TREE_SIGNATURES,
                               **SOLVE_HASH_SIGNATURES, **SOLVE_WINDOW_SIGNATURES, **MOVES_SIGNATURES,
                               **BUDGET_SIGNATURES, **LINE_SIGNATURES, **PLAY_SOLVE_SIGNATURES,
-                              **PERFT_SIGNATURES, **MCTS_SIGNATURES, **MCTS_TREE_SIGNATURES}.items():
+                              **PERFT_SIGNATURES, **MCTS_SIGNATURES, **MCTS_TREE_SIGNATURES,
+                              **MCTS_WIDE_SIGNATURES}.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -72,6 +72,13 @@ struct SlabTree {
         ns[v] = make_uint2(w.x + n, w.y + s);
         dl[v].x += (u32)d;
     }
+    // the wide search's two halves of add_stats (mcts_wide_core.hpp): the visit by the one wave that selects; the
+    // sums by any wave of the block, as vector atomics that return nothing (integer adds: any order, the same words)
+    __device__ __forceinline__ void mark(u32 v) { ns[v].x += 1u; }
+    __device__ __forceinline__ void add_result(u32 v, u32 s, int d) {
+        __hip_atomic_fetch_add(&ns[v].y, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(&dl[v].x, (u32)d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
     // a phase's writes, made by one lane, before the next phase's reads by another lane of this wave
     // (the explicit wait after the fence: the stores are complete, not only ordered, before the wave goes on)
     __device__ __forceinline__ void sync() const {

@@ -88,6 +88,10 @@ re-roots the tree on that move and keeps the playouts below it, and every ``go``
 runs T more iterations on what is left.  A new game, or a position the tree
 does not stand at, starts a tree from one node; the k-th such start (from 0)
 takes the ids from k * 2**40.  The tree has room for 1 + 32 T nodes.
+``--leaves L`` (with ``--policy mcts``, 1..16; not with ``--reuse 1``) makes
+every ``go`` the wide search, ops.mcts(..., leaves=L): ``--iterations`` is then
+the number R of rounds of L leaves each, R L at most 65536, one block of L waves
+on the position, and the k-th ``go`` takes the ids from k * R * L * 64.
 """
 import argparse
 import random
@@ -104,7 +108,7 @@ from .codec import handstr_from_coord
 class Engine:
     def __init__(self, name="GPU", policy="greedy", seed=0, weights=None, solve_empties=0, depth=1, split=0, order=0,
                  solve_task_empties=None, solve_order=None, solve_hash_bits=None, solve_wld_empties=0, nodes=None,
-                 iterations=None, explore=0.5, reuse=0):
+                 iterations=None, explore=0.5, reuse=0, leaves=None):
         top = _lib.SOLVE_MAX_EMPTIES if solve_task_empties is None else _lib.SOLVE_TREE_MAX_EMPTIES
         if not 0 <= solve_empties <= top:
             raise ValueError(f"solve_empties must lie in 0..{top}" + (
@@ -144,6 +148,15 @@ class Engine:
                 raise ValueError(f"policy mcts needs iterations in 1..{_lib.MCTS_MAX_ITERATIONS}")
         elif iterations is not None:
             raise ValueError("iterations applies to policy mcts")
+        if leaves is not None:
+            if policy != "mcts":
+                raise ValueError("leaves applies to policy mcts")
+            if reuse:
+                raise ValueError("leaves applies to a search from one node: not with reuse")
+            if not 1 <= leaves <= _lib.MCTS_WIDE_MAX_LEAVES or iterations * leaves > _lib.MCTS_MAX_ITERATIONS:
+                raise ValueError(f"leaves must lie in 1..{_lib.MCTS_WIDE_MAX_LEAVES}, iterations x leaves in "
+                                 f"1..{_lib.MCTS_MAX_ITERATIONS}")
+        self.leaves = leaves
         if reuse not in (0, 1):
             raise ValueError("reuse must be 0 or 1")
         if reuse and policy != "mcts":
@@ -265,7 +278,7 @@ class Engine:
             r = self._trees.search(self.iterations, explore=self.explore, seed=self.seed)
         else:
             r = ops.mcts(boards, side, self.iterations, explore=self.explore, seed=self.seed,
-                         game_id0=self.go_index * self.iterations * 64)
+                         game_id0=self.go_index * self.iterations * (self.leaves or 1) * 64, leaves=self.leaves)
             self.go_index += 1
         sq = int(r.best_move.cpu()[0])
         if int(r.status.cpu()[0]) != _lib.MCTS_SEARCHED or sq > 63:
@@ -430,7 +443,7 @@ class Engine:
             extra = " weights=%s" % self.weights.reshape(-1).tolist() if self.policy in ("eval", "search") else ""
             if self.policy == "mcts":
                 extra = " iterations=%d explore=%g" % (self.iterations, self.explore) + (
-                    " reuse=1" if self.reuse else "")
+                    " reuse=1" if self.reuse else "") + (" leaves=%d" % self.leaves if self.leaves else "")
             if self.policy == "search":
                 extra = " depth=%d" % self.depth + (" nodes=%d" % self.nodes if self.nodes is not None else "") + (
                     " split=%d" % self.split if self.split > 0 else "") + (
@@ -506,9 +519,15 @@ def main(argv=None):
     p.add_argument("--explore", type=float, default=0.5, metavar="C", help="policy mcts: UCT's exploration constant")
     p.add_argument("--reuse", type=int, default=0, choices=[0, 1],
                    help="policy mcts: 1 keeps the search tree between moves, re-rooted on every move played")
+    p.add_argument("--leaves", type=int, default=None, metavar="L",
+                   help="policy mcts: the wide search, --iterations rounds of L leaves each, a block of L waves (1..16)")
     a = p.parse_args(argv)
     if a.policy != "mcts" and a.reuse:
         p.error("--reuse applies to --policy mcts")
+    if a.policy != "mcts" and a.leaves is not None:
+        p.error("--leaves applies to --policy mcts")
+    if a.leaves is not None and a.reuse:
+        p.error("--leaves is not for --reuse 1: the trees that persist have one leaf an iteration")
     if a.policy == "mcts" and a.iterations is None:
         p.error("--policy mcts needs --iterations")
     if a.policy != "mcts" and a.iterations is not None:
@@ -518,7 +537,7 @@ def main(argv=None):
     weights = params.read_paramgen(a.params)[1] if a.params else None
     eng = Engine(a.name, a.policy, a.seed, weights, a.solve_empties, a.depth, a.split, a.order,
                  a.solve_task_empties, a.solve_order, a.solve_hash_bits, a.solve_wld_empties, a.nodes, a.iterations,
-                 a.explore, a.reuse)
+                 a.explore, a.reuse, a.leaves)
 
     def out(s):
         sys.stdout.write(s + "\n")

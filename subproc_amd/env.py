@@ -139,12 +139,14 @@ class VecEnv:
         return ops.perft(self.boards, self.turn, depth, split=split, want_divide=want_divide, want_nodes=want_nodes,
                          node_limit=node_limit, max_tasks=max_tasks)
 
-    def mcts(self, iterations, explore=0.5, seed=0, game_id0=0, max_nodes=None, log_table=None, want_nodes=False):
+    def mcts(self, iterations, explore=0.5, seed=0, game_id0=0, max_nodes=None, log_table=None, want_nodes=False,
+             leaves=None):
         """Monte Carlo tree search from the current state (ops.mcts): per game
         `iterations` iterations of 64 random playouts, the visits, half-points
-        and disc sums of every root move and the most visited move."""
+        and disc sums of every root move and the most visited move.  `leaves`
+        = L: the wide search, `iterations` rounds of L leaves each."""
         return ops.mcts(self.boards, self.turn, iterations, explore=explore, seed=seed, game_id0=game_id0,
-                        max_nodes=max_nodes, log_table=log_table, want_nodes=want_nodes)
+                        max_nodes=max_nodes, log_table=log_table, want_nodes=want_nodes, leaves=leaves)
 
     def mcts_trees(self, max_nodes, id_base=None, game_id0=0, stride=0):
         """Search trees that persist, one per game, rooted at the current state

@@ -976,7 +976,8 @@ def _log_table_on(T, d):
     return t
 
 
-def mcts(boards, turn, iterations, explore=0.5, seed=0, game_id0=0, max_nodes=None, log_table=None, want_nodes=False):
+def mcts(boards, turn, iterations, explore=0.5, seed=0, game_id0=0, max_nodes=None, log_table=None, want_nodes=False,
+         leaves=None):
     """Monte Carlo tree search (othu_mcts, include/othello_mcts.h): UCT over
     uniform random playouts, ``iterations`` = T (1..65536) iterations of 64
     playouts from every position for its mover (White if turn == 2, else
@@ -1011,10 +1012,27 @@ def mcts(boards, turn, iterations, explore=0.5, seed=0, game_id0=0, max_nodes=No
     synchronisation) and nothing is read on the host, so with the table on the
     device (``log_table`` passed in, or an earlier call with this T) the call
     may be captured in a graph -- the scratch then belongs to the graph's pool.
+
+    ``leaves`` = L (1..16; None, the default: the call above and nothing else)
+    runs the wide search (othv_mcts_wide, include/othello_mcts_wide.h):
+    ``iterations`` = R rounds, each of L walkers that select one after another,
+    every visit pending on a walker's path counting as a loss for the later
+    ones, then L x 64 playouts, one wave per walker and one block of L waves
+    per tree, backed up into the same tree.  The tree gets R L leaf visits
+    (1..65536), so R L stands for T above: in the default ``max_nodes``, in the
+    table's R L + 1 entries, in ``root_wins``.  Walker w of round r of position
+    i plays the ids ``game_id0 + ((i R + r) L + w) 64 + j``; row i of a batch
+    is the single call with ``game_id0 + i R L 64``.  The answer depends on L;
+    with L = 1 it is the answer without ``leaves``.
     """
-    T = int(iterations)
-    if not 1 <= T <= _lib.MCTS_MAX_ITERATIONS:
-        raise ValueError(f"iterations must lie in 1..{_lib.MCTS_MAX_ITERATIONS}")
+    R = int(iterations)
+    L = None if leaves is None else int(leaves)
+    if L is not None and not 1 <= L <= _lib.MCTS_WIDE_MAX_LEAVES:
+        raise ValueError(f"leaves must lie in 1..{_lib.MCTS_WIDE_MAX_LEAVES}")
+    T = R if L is None else R * L
+    if R < 1 or not 1 <= T <= _lib.MCTS_MAX_ITERATIONS:
+        raise ValueError(f"iterations must lie in 1..{_lib.MCTS_MAX_ITERATIONS}" +
+                         ("" if L is None else ", iterations x leaves too"))
     M = min(1 + 16 * T, _lib.MCTS_MAX_NODES) if max_nodes is None else int(max_nodes)
     if not 1 <= M <= _lib.MCTS_MAX_NODES:
         raise ValueError(f"max_nodes must lie in 1..{_lib.MCTS_MAX_NODES}")
@@ -1028,18 +1046,22 @@ def mcts(boards, turn, iterations, explore=0.5, seed=0, game_id0=0, max_nodes=No
     table = _log_table_on(T, d) if log_table is None else log_table
     plt = _dev(table, "log_table", torch.float32, (T + 1,), d)
     lib = _lib.load()
-    size = lib.othu_mcts_scratch_bytes(n, M)
+    size = lib.othu_mcts_scratch_bytes(n, M) if L is None else lib.othv_mcts_wide_scratch_bytes(n, M, L)
     if size < 0:
-        check(int(size), "othu_mcts_scratch_bytes")
+        check(int(size), "othu_mcts_scratch_bytes" if L is None else "othv_mcts_wide_scratch_bytes")
     rows = [torch.empty((n, 64), dtype=torch.int32, device=d) for _ in range(3)]
     root = [torch.empty(n, dtype=torch.int32, device=d) for _ in range(2)]
     mv, st = (torch.empty(n, dtype=torch.uint8, device=d) for _ in range(2))
     nd = torch.empty(n, dtype=torch.int32, device=d) if want_nodes else None
     scratch = torch.empty(max(int(size), 16) // 8, dtype=torch.int64, device=d)
+    tail = (c, plt, int(seed) & (2**64 - 1), int(game_id0) & (2**64 - 1), M, *(r.data_ptr() for r in rows),
+            *(r.data_ptr() for r in root), mv.data_ptr(), st.data_ptr(), _ptr(nd), scratch.data_ptr(),
+            scratch.numel() * 8, n)
     with torch.cuda.device(d):
-        check(lib.othu_mcts(pb, pt, T, c, plt, int(seed) & (2**64 - 1), int(game_id0) & (2**64 - 1), M,
-                            *(r.data_ptr() for r in rows), *(r.data_ptr() for r in root), mv.data_ptr(), st.data_ptr(),
-                            _ptr(nd), scratch.data_ptr(), scratch.numel() * 8, n, _stream()), "othu_mcts")
+        if L is None:
+            check(lib.othu_mcts(pb, pt, T, *tail, _stream()), "othu_mcts")
+        else:
+            check(lib.othv_mcts_wide(pb, pt, R, L, *tail, _stream()), "othv_mcts_wide")
     # (the caching allocator hands the scratch to later work of THIS stream only)
     return MctsResult(*rows, *root, mv, st, nd)
 

@@ -79,6 +79,8 @@ struct HostTree {
     void set_stats(u32 v, u32 n, u32 s, int d) { nn.at(v) = n, ss.at(v) = s, dd.at(v) = d; }
     void set_link(u32 v, u32 l) { link_.at(v) = l; }
     void add_stats(u32 v, u32 n, u32 s, int d) { nn.at(v) += n, ss.at(v) += s, dd.at(v) += d; }
+    void mark(u32 v) { nn.at(v) += 1; }  // the wide search's two halves of add_stats (mcts_wide_core.hpp)
+    void add_result(u32 v, u32 s, int d) { ss.at(v) += s, dd.at(v) += d; }
     void sync() const {}
 };
 
